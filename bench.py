@@ -15,19 +15,23 @@ round-robin (SRT_RENDER_SHARDED), every rank draws the same stream and reads its
 tiles are gathered to rank 0 over RCCL (xGMI) and every rank keeps its rows of the linear RGB in its
 HBM; the frame is fixed, so scaling is strong.  `--rgb-to-host` copies the linear RGB to pinned host
 memory as well (rounds 1-4's step: 50 MB per 1080p frame over PCIe, every rank its own rows at
-N > 1); the default line reports that form too (`host_rgb`).  Two launches, no
+N > 1); the `--full` line reports that form too (`host_rgb`).  Two launches, no
 torch imported in either: one process per GPU (WORLD_SIZE set by a launcher such as the driver's
 `torch.distributed.run`; the ranks meet through the library's srt_comm_init), or -- `--gpus N` with no
 launcher -- this one process driving all N GPUs through the library's group (srt_comm_init_all +
 pipelined srt_render_group).
 
-Secondary figures in the same line: `host_rgb` (the same frames with the linear RGB copied to host
-memory too), `frame_latency_ms` (one synchronous frame), `device_resident`
+A plain run sets up, warms up, times the K steps and prints the line (`--dump-outputs DIR` also writes
+what the last timed frame handed back, as DIR/<name>.npy).  Everything else runs only with `--full`.
+
+Secondary figures in the same line with `--full`: `host_rgb` (the same frames with the linear RGB
+copied to host memory too), `frame_latency_ms` (one synchronous frame), `device_resident`
 (jitter pre-resident in HBM and outputs left in HBM: the round-1 headline), the roofline of the
 dominant kernel, and the CPU baseline (oracle: one core, and a multiprocessing.Pool over samples
 structured like the reference's Scene.render).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config example1_1080p_d5] [--rng mt|device]
+                    [--full] [--dump-outputs DIR]
 """
 import os
 
@@ -350,6 +354,34 @@ def comm_id_exchange(lib, N, rank, world):
     return buf, path
 
 
+DUMP_BYTES = 64 << 20  # most that --dump-outputs writes in all
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: every array of `arrays` (name -> ndarray) as directory/<name>.npy in float32
+    (float64 stays float64), whole if the arrays fit DUMP_BYTES together; else each keeps an equal
+    share of it as a fixed sample of its flattened elements (sorted indices from default_rng(0), the
+    same for equal sizes from run to run)."""
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    conv = {k: np.asarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    if sum(v.nbytes for v in conv.values()) > DUMP_BYTES:
+        share = DUMP_BYTES // len(conv) - 4096  # (room for the .npy headers)
+        for k, v in conv.items():
+            if v.nbytes > share:
+                idx = np.sort(np.random.default_rng(0).integers(0, v.size, share // v.itemsize))
+                conv[k] = v.reshape(-1)[idx]
+    for k, v in conv.items():
+        np.save(out / (k + ".npy"), v)
+
+
+def host_array(addr, dtype, shape):
+    """A copy of the host buffer at `addr` as an ndarray."""
+    n = int(np.prod(shape))
+    return np.frombuffer((ctypes.c_char * (n * np.dtype(dtype).itemsize)).from_address(addr), dtype=dtype).reshape(
+        shape).copy()
+
+
 def visible_gpus():
     """GPUs this process may use, counted WITHOUT initialising HIP (the launcher below must not touch
     the GPU before it starts the ranks): KFD topology nodes with SIMDs (GPU agents), capped by the
@@ -482,6 +514,14 @@ def run_group(args, gpus):
 
     el, last = timed(args.rgb_to_host)
     ms_step = el / args.steps * 1e3
+    if args.dump_outputs:
+        # the last timed frame as rank 0's caller has it: the uint8 image, and the linear RGB if it
+        # came to the host
+        u8, rgb = outs[(frame["k"] - 1) % NOUT]
+        got = {"srgb8": host_array(u8.value, np.uint8, (W * H, 3))}
+        if args.rgb_to_host:
+            got["rgb"] = host_array(rgb.value, np.float64, (3, W * H))
+        dump_outputs(args.dump_outputs, got)
     rec = {
         "metric": "Mrays/sec (primary+secondary) + frame ms at 1920x1080 depth 5" if args.config == "example1_1080p_d5"
         else "Mrays/sec (primary+secondary) + frame ms",
@@ -537,8 +577,17 @@ def main():
     ap.add_argument("--config", default="example1_1080p_d5", choices=sorted(CONFIGS))
     ap.add_argument("--rng", default="mt", choices=["mt", "device"],
                     help="mt: the reference's numpy stream generated on the GPU inside every step; device: Philox")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the latency / device-resident / roofline runs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what stands beside the headline figure: the host-RGB frames, the frame "
+                         "latency, the device-resident frames, the roofline of the dominant kernel and the CPU "
+                         "baseline (default: the timed steps and the result line only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed frame handed back as DIR/<name>.npy: "
+                         "srgb8 (the uint8 image, as float32) and, with --rgb-to-host, rgb (the linear RGB, float64); "
+                         "at most 64 MB in all (a fixed seeded sample of each array beyond that)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="with --full: skip the latency / device-resident / roofline runs")
     ap.add_argument("--spp", type=int, default=None)
     ap.add_argument("--size", default=None, help="diagnostic: WxH override of the config's frame size")
     ap.add_argument("--option", action="append", default=[],
@@ -570,6 +619,8 @@ def main():
     ap.add_argument("--shard-bands", type=int, default=0,
                     help="most row bands per rank (library option shard_bands; default rt_device.h shard_kmax)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_secondary = args.no_cpu_baseline = True
     if not 1 <= args.hw_queues <= 32:
         raise SystemExit("bench.py: --hw-queues 1 .. 32")
     os.environ["GPU_MAX_HW_QUEUES"] = str(args.hw_queues)  # (before anything initialises HIP)
@@ -722,6 +773,22 @@ def main():
         enq.append(enq_ms)
         rank_ms.append(el / args.steps * 1e3)
         rank_rays.append(last["total_rays"])
+    if args.dump_outputs and rank == 0:
+        # the last timed frame as the caller has it: the uint8 image (rank 0's), and the linear RGB if
+        # it came to the host (--device-outputs: both read back from HBM)
+        u8, rgb = outs[(frame["k"] - 1) % NOUT]
+        n_rgb = W * H if world > 1 else npix_full
+        if args.device_outputs and world == 1:
+            got = {"srgb8": np.empty((npix_full, 3), np.uint8)}
+            N.check(lib, lib.srt_memcpy(ctx, N.ptr(got["srgb8"]), u8, got["srgb8"].nbytes))
+            if args.rgb_to_host:
+                got["rgb"] = np.empty((3, npix_full), np.float64)
+                N.check(lib, lib.srt_memcpy(ctx, N.ptr(got["rgb"]), rgb, got["rgb"].nbytes))
+        else:
+            got = {"srgb8": host_array(u8.value, np.uint8, (npix_full, 3))}
+            if args.rgb_to_host:
+                got["rgb"] = host_array(rgb.value, np.float64, (3, n_rgb))
+        dump_outputs(args.dump_outputs, got)
     elapsed = max(rank_ms) * args.steps / 1e3
     if len(rehearse) > 1:
         last["total_rays"] = sum(rank_rays)

@@ -1,4 +1,4 @@
-"""Pre-flight of the driver's 8-GPU run on the CPU: `bench.py --gpus 8 --steps K --warmup W`, both ways
+"""Pre-flight of the driver's 8-GPU run on the CPU: `bench.py --gpus 8 --steps K --warmup W --full`, both ways
 the driver may start it, against tests/fake_srt.py (the C ABI restated in Python, checking every
 call) instead of libsightpy_hip.so:
 
@@ -56,8 +56,8 @@ def test_bench_gpus_8_one_process_per_rank(tmp_path, extra):
     shared frame and tile it exactly; the JSON line comes from rank 0 alone, n_gpus = nranks = 8,
     value = the 8 ranks' rays / the slowest rank's time."""
     W, H, spp, world = 96, 64, 2, 8
-    argv = ["--gpus", "8", "--steps", "4", "--warmup", "2", "--config", "example1_1080p_d5", "--size", "%dx%d" % (W, H),
-            "--spp", str(spp)] + extra
+    argv = ["--gpus", "8", "--steps", "4", "--warmup", "2", "--full", "--config", "example1_1080p_d5",
+            "--size", "%dx%d" % (W, H), "--spp", str(spp)] + extra
     port = str(20000 + os.getpid() % 20000)
     procs = []
     for r in range(world):
@@ -111,8 +111,8 @@ def test_bench_gpus_8_in_process_group(tmp_path, monkeypatch, capsys):
         monkeypatch.setattr(bench, "visible_gpus", lambda: 8)
         for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
             monkeypatch.delenv(k, raising=False)
-        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "4", "--warmup", "2", "--size",
-                                          "%dx%d" % (W, H), "--spp", str(spp)])
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "4", "--warmup", "2", "--full",
+                                          "--size", "%dx%d" % (W, H), "--spp", str(spp)])
         bench.main()
     finally:
         sys.path.remove(str(ROOT))
@@ -134,8 +134,8 @@ def test_bench_gpus_8_line_survives_a_failed_secondary_figure(tmp_path):
     prints its one JSON line, with the timed value and the error in `secondary_error`, and every rank
     exits cleanly (the ranks take the same branch, no collective is left waiting)."""
     W, H, spp, world = 96, 64, 2, 8
-    argv = ["--gpus", "8", "--steps", "4", "--warmup", "2", "--config", "example1_1080p_d5", "--size", "%dx%d" % (W, H),
-            "--spp", str(spp)]
+    argv = ["--gpus", "8", "--steps", "4", "--warmup", "2", "--full", "--config", "example1_1080p_d5",
+            "--size", "%dx%d" % (W, H), "--spp", str(spp)]
     port = str(20000 + (os.getpid() + 7919) % 20000)
     procs = []
     for r in range(world):
@@ -159,3 +159,79 @@ def test_bench_gpus_8_line_survives_a_failed_secondary_figure(tmp_path):
     rec = lines[0][0]
     assert rec["n_gpus"] == world and rec["value"] > 0
     assert "injected" in rec["secondary_error"] and "host_rgb" not in rec
+
+
+@pytest.mark.parametrize("warmup,extra", [(2, []), (0, ["--rgb-to-host"])])
+def test_plain_run_renders_only_its_steps_and_dumps_the_last_frame(tmp_path, monkeypatch, capsys, warmup, extra):
+    """Without --full the bench renders the warm-up and the timed frames and nothing else (no host-RGB,
+    latency or lane-statistics frames, no CPU baseline); --dump-outputs writes the last timed frame's
+    arrays: the uint8 image as float32 and, with --rgb-to-host, the linear RGB as float64."""
+    sys.path[:0] = [str(ROOT), str(HERE)]
+    try:
+        import bench
+        import fake_srt
+        from sightpy import _backend as B
+
+        W, H, spp = 96, 64, 2
+        fake = fake_srt.FakeSrt(W, H, spp, 8, 0, str(tmp_path), group=True)
+        monkeypatch.setitem(B._STATE, "lib", fake)
+        monkeypatch.setattr(bench, "visible_gpus", lambda: 8)
+        monkeypatch.setattr(bench, "cpu_baseline", None)  # (calling it would raise)
+        for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+            monkeypatch.delenv(k, raising=False)
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "4", "--warmup", str(warmup), "--size",
+                                          "%dx%d" % (W, H), "--spp", str(spp), "--dump-outputs",
+                                          str(tmp_path / "dump")] + extra)
+        bench.main()
+    finally:
+        sys.path.remove(str(ROOT))
+        sys.path.remove(str(HERE))
+    import numpy as np
+
+    lines = [json.loads(ln) for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    rec = lines[0]
+    assert rec["steps"] == 4 and rec["ms_per_step"] > 0 and rec["dtype"] == "f64"
+    assert not {"host_rgb", "roofline", "device_resident", "cpu_baseline"} & set(rec)
+    assert "frame_latency_ms" not in rec["config"]
+    assert "errors" not in fake.log, fake.log.get("errors")
+    assert len(fake.frames) == warmup + 4
+    assert sorted(p.name for p in (tmp_path / "dump").iterdir()) == (["rgb.npy"] if extra else []) + ["srgb8.npy"]
+    u8 = np.load(tmp_path / "dump" / "srgb8.npy")
+    assert u8.dtype == np.float32 and u8.shape == (W * H, 3)
+    if not extra:
+        return
+    rgb = np.load(tmp_path / "dump" / "rgb.npy")
+    assert rgb.dtype == np.float64 and rgb.shape == (3, W * H)
+    from sightpy._shard import shard_kmax, shard_rows
+
+    want = np.empty(H)
+    for q in range(8):
+        want[shard_rows(H, 8, q, shard_kmax(H, 8, 0, 1))] = q + 1  # (the stand-in writes owner + 1)
+    assert np.array_equal(rgb.reshape(3, H, W), np.broadcast_to(want[None, :, None], (3, H, W)))
+
+
+def test_dump_outputs_samples_beyond_its_budget(tmp_path, monkeypatch):
+    """Arrays that do not fit the budget together are each cut to a fixed sample (the same from run to
+    run) of an equal share of it; arrays that fit are written whole."""
+    sys.path.insert(0, str(ROOT))
+    try:
+        import bench
+    finally:
+        sys.path.remove(str(ROOT))
+    import numpy as np
+
+    a = np.arange(30000, dtype=np.uint8).reshape(-1, 3)
+    b = np.linspace(0.0, 1.0, 30000)
+    bench.dump_outputs(tmp_path / "whole", {"a": a, "b": b})
+    assert np.array_equal(np.load(tmp_path / "whole" / "a.npy"), a.astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "whole" / "b.npy"), b)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 100000)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(tmp_path / d, {"a": a, "b": b})
+    files = [tmp_path / d / n for d in ("s1", "s2") for n in ("a.npy", "b.npy")]
+    assert sum(f.stat().st_size for f in files[:2]) <= 100000
+    sa, sb = np.load(files[0]), np.load(files[1])
+    assert sa.dtype == np.float32 and sb.dtype == np.float64 and 0 < sb.size < b.size
+    assert np.isin(sb, b).all() and np.isin(sa, a).all()
+    assert np.array_equal(sa, np.load(files[2])) and np.array_equal(sb, np.load(files[3]))

@@ -1,27 +1,29 @@
-"""The reference's own example scripts run unchanged against this package (BASELINE.json north_star:
-"example*.py run unchanged"), and the scenes they build are exactly the ones tests/scenes.py
-restates for the tests and the bench.
+"""The scenes the reference's own example scripts build against this package (BASELINE.json
+north_star: "example*.py run unchanged") are exactly the ones tests/scenes.py restates for the tests
+and the bench.
 
-Each script under /root/reference (example1.py, example2.py, example3.py, example4.py,
-example_cornellbox.py) is executed in place with `runpy`, with `import sightpy` resolving to THIS
-package (python-raytracer_amd/sightpy).  Nothing is edited; only `Scene.add_Camera` is wrapped to
-shrink the frame and `Scene.render` is intercepted to capture the scene and its arguments (no
-image is rendered or written).  The captured scene is lowered with `_lower.lower_scene` -- the
-tables the device renders from -- and compared field by field with the lowering of the matching
-tests/scenes.py builder, so the restated scenes cannot drift from the scripts.
+tests/golden/example_scripts.npz records what each script (example1.py, example2.py, example3.py,
+example4.py, example_cornellbox.py) built when it was executed unchanged with `runpy`, with
+`import sightpy` resolving to THIS package (python-raytracer_amd/sightpy): only `Scene.add_Camera`
+was wrapped to shrink the frame and `Scene.render` intercepted to capture the scene and its arguments
+(no image rendered or written).  The captured scene was lowered with `_lower.lower_scene` -- the
+tables the device renders from -- and stored with its camera and the script's samples_per_pixel
+(texel arrays as shape, dtype and SHA-256).  The test lowers the matching tests/scenes.py builder and
+compares it with the record field by field, so the restated scenes cannot drift from the scripts.
 
-CPU only.  The reference exists only in the build container: without /root/reference the test is
-skipped (it never runs on the GPU box).
+CPU only.  To record the fixture again from a checkout of the reference:
+
+    python tests/test_examples_unchanged.py REFERENCE_DIR
 """
+import hashlib
 import runpy
+import sys
 from pathlib import Path
 
 import numpy as np
 import pytest
 
-import scenes
-
-REF = Path("/root/reference")
+GOLDEN = Path(__file__).resolve().parent / "golden" / "example_scripts.npz"
 W, H = 40, 30
 
 # script -> (tests/scenes.py builder, samples_per_pixel the script renders with)
@@ -33,15 +35,18 @@ SCRIPTS = {
     "example_cornellbox.py": ("cornell", None),
 }
 
-pytestmark = pytest.mark.skipif(not REF.is_dir(), reason="the reference exists only in the build container")
+TABLES = ("colliders", "materials", "textures", "lights")
+ARRAYS = ("media", "glossy_f0", "light_local", "importance", "texels")
+HASHED = ("texels",)  # too large to store: recorded as shape, dtype and digest
 
 
 class _Captured(Exception):
     pass
 
 
-def run_script(script):
-    """Execute the reference script against this package; return (scene, render args, kwargs)."""
+def run_script(ref, script):
+    """Execute the reference script `ref / script` against this package; return (scene, render args,
+    kwargs)."""
     import sightpy
 
     assert Path(sightpy.__file__).resolve().parent.parent.name == "python-raytracer_amd"
@@ -58,7 +63,7 @@ def run_script(script):
 
     sightpy.Scene.add_Camera, sightpy.Scene.render = add_camera, render
     try:
-        runpy.run_path(str(REF / script), run_name="__main__")
+        runpy.run_path(str(Path(ref) / script), run_name="__main__")
     except _Captured:
         pass
     finally:
@@ -67,57 +72,95 @@ def run_script(script):
     return box["scene"], box["args"], box["kwargs"]
 
 
-def _fields(rec):
-    return {name: rec[name] for name in rec.dtype.names}
+def _digest(a):
+    a = np.ascontiguousarray(a)
+    return np.frombuffer(hashlib.sha256(a.tobytes()).digest(), dtype=np.uint8)
 
 
-def assert_same_lowering(a, b):
-    from sightpy import _lower
+def snapshot(sc):
+    """What the device renders `sc` from, as plain arrays: the lowered tables, every field of the
+    camera description but its two pointers, and the camera's pixel grids."""
+    from sightpy import _backend as B, _lower
 
-    la, lb = _lower.lower_scene(a), _lower.lower_scene(b)
-    for name in ("colliders", "materials", "textures", "lights"):
-        ra, rb = getattr(la, name), getattr(lb, name)
-        assert ra.dtype == rb.dtype and len(ra) == len(rb), name
-        for i in range(len(ra)):
-            fa, fb = _fields(ra[i]), _fields(rb[i])
-            for f in fa:
-                va, vb = np.asarray(fa[f]), np.asarray(fb[f])
-                assert np.array_equal(va, vb, equal_nan=va.dtype.kind == "f"), (name, i, f)
-    for name in ("media", "glossy_f0", "light_local", "importance", "texels"):
-        va, vb = getattr(la, name), getattr(lb, name)
-        if va is None or vb is None:
-            assert va is None and vb is None, name
+    lo = _lower.lower_scene(sc)
+    out = {name: np.asarray(getattr(lo, name)) for name in TABLES}
+    for name in ARRAYS:
+        v = getattr(lo, name)
+        out["has_" + name] = np.asarray(v is not None)
+        if v is None:
             continue
-        va, vb = np.asarray(va), np.asarray(vb)
-        assert va.shape == vb.shape and np.array_equal(va, vb, equal_nan=va.dtype.kind in "fc"), name
-    assert la.ambient == lb.ambient
-    assert la.max_ray_depth == lb.max_ray_depth
-    assert la.has_diffuse == lb.has_diffuse
-
-
-def assert_same_camera(a, b):
-    from sightpy import _backend as B
-
-    ca, cb = B.camera_desc(a.camera), B.camera_desc(b.camera)
-    for f, _ in ca._fields_:
+        v = np.asarray(v)
+        if name in HASHED:
+            out[name + "_shape"] = np.asarray(v.shape, dtype=np.int64)
+            out[name + "_dtype"] = np.asarray(v.dtype.str)
+            out[name + "_sha256"] = _digest(v)
+        else:
+            out[name] = v
+    out["ambient"] = np.asarray(lo.ambient, dtype=np.float64)
+    out["max_ray_depth"] = np.asarray(lo.max_ray_depth)
+    out["has_diffuse"] = np.asarray(lo.has_diffuse)
+    cd = B.camera_desc(sc.camera)
+    for f, _ in cd._fields_:
         if f in ("xs", "ys"):
             continue
-        va, vb = getattr(ca, f), getattr(cb, f)
-        if hasattr(va, "__len__"):
-            va, vb = list(va), list(vb)
-        assert va == vb, f
-    assert np.array_equal(a.camera.x, b.camera.x) and np.array_equal(a.camera.y, b.camera.y)
+        v = getattr(cd, f)
+        out["camera_" + f] = np.asarray(list(v) if hasattr(v, "__len__") else v)
+    out["camera_x"], out["camera_y"] = np.asarray(sc.camera.x), np.asarray(sc.camera.y)
+    return out
+
+
+def assert_same_snapshot(a, b):
+    assert set(a) == set(b), sorted(set(a) ^ set(b))
+    for name in sorted(a):
+        va, vb = a[name], b[name]
+        assert va.dtype == vb.dtype and va.shape == vb.shape, name
+        if va.dtype.names:
+            for i in range(len(va)):
+                for f in va.dtype.names:
+                    fa, fb = np.asarray(va[i][f]), np.asarray(vb[i][f])
+                    assert np.array_equal(fa, fb, equal_nan=fa.dtype.kind == "f"), (name, i, f)
+        else:
+            assert np.array_equal(va, vb, equal_nan=va.dtype.kind in "fc"), name
+
+
+@pytest.fixture(scope="module")
+def recorded():
+    with np.load(GOLDEN, allow_pickle=False) as z:
+        return {k: z[k] for k in z.files}
 
 
 @pytest.mark.parametrize("script", sorted(SCRIPTS))
-def test_reference_example_runs_unchanged_and_matches_restated_scene(script):
+def test_reference_example_runs_unchanged_and_matches_restated_scene(script, recorded):
+    import scenes
+
     builder, spp = SCRIPTS[script]
-    sc, args, kwargs = run_script(script)
+    got = {k[len(builder) + 1:]: v for k, v in recorded.items() if k.startswith(builder + "/")}
+    got_spp = int(got.pop("samples_per_pixel"))
+    assert (got.pop("width"), got.pop("height")) == (W, H)
     want = getattr(scenes, builder)(W, H, None)
-    assert_same_camera(sc, want)
-    assert_same_lowering(sc, want)
-    got_spp = kwargs.get("samples_per_pixel", args[0] if args else None)
+    assert_same_snapshot(got, snapshot(want))
     if spp is not None:
         assert got_spp == spp
     else:
-        assert isinstance(got_spp, int) and got_spp > 0
+        assert got_spp > 0
+
+
+def record(ref):
+    """Run every script of the reference checkout `ref` against this package and store what it built."""
+    here = Path(__file__).resolve().parent
+    sys.path[:0] = [str(here.parent / "python-raytracer_amd"), str(here)]
+    out = {}
+    for script, (builder, _) in sorted(SCRIPTS.items()):
+        sc, args, kwargs = run_script(ref, script)
+        spp = kwargs.get("samples_per_pixel", args[0] if args else None)
+        assert isinstance(spp, int) and spp > 0, script
+        rec = snapshot(sc)
+        rec.update(samples_per_pixel=np.asarray(spp), width=np.asarray(W), height=np.asarray(H))
+        out.update({builder + "/" + k: v for k, v in rec.items()})
+        print(script, "->", builder, len(rec), "arrays")
+    np.savez_compressed(GOLDEN, **out)
+    print(GOLDEN.name, GOLDEN.stat().st_size, "bytes")
+
+
+if __name__ == "__main__":
+    record(sys.argv[1])

@@ -21,17 +21,17 @@ for step in "$@"; do
   case $step in
     smoke) run smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()" ;;
     tests) run tests 900 python3 -u -m pytest tests -x -v -m gpu --timeout 300 --timeout-method thread -rf ;;
-    bench) run bench 600 python3 bench.py ;;
-    bench_nocpu) run bench_nocpu 300 python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline ;;
-    shard8) for n in 2 4 8; do run "bench_shard$n" 300 python3 bench.py --no-cpu-baseline --shard-of $n; done ;;
+    bench) run bench 600 python3 bench.py --full ;;
+    bench_nocpu) run bench_nocpu 300 python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline ;;
+    shard8) for n in 2 4 8; do run "bench_shard$n" 300 python3 bench.py --full --no-cpu-baseline --shard-of $n; done ;;
     prof) run prof 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o bench --output-format csv -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline ;;
     pmc_fetch) run pmc_fetch_${CONFIG:-example1_1080p_d5} 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d gpurun_out/pmc_fetch_${CONFIG:-example1_1080p_d5} -o bench --output-format csv -- python3 bench.py --config ${CONFIG:-example1_1080p_d5} --steps 3 --warmup 1 --no-cpu-baseline ;;
     pmc_write) run pmc_write_${CONFIG:-example1_1080p_d5} 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d gpurun_out/pmc_write_${CONFIG:-example1_1080p_d5} -o bench --output-format csv -- python3 bench.py --config ${CONFIG:-example1_1080p_d5} --steps 3 --warmup 1 --no-cpu-baseline ;;
-    configs_long) run bench_example3_1080p_d8 600 python3 bench.py --config example3_1080p_d8 --steps 100 --warmup 20
-                  run bench_example4_4k_d6 600 python3 bench.py --config example4_4k_d6 --steps 20 --warmup 5
-                  run bench_cornell_800_s512 900 python3 bench.py --config cornell_800_s512 --steps 2 --warmup 1
-                  run bench_mesh_1080p_d3 600 python3 bench.py --config mesh_1080p_d3 --steps 100 --warmup 20 ;;
-    configs) for c in example3_1080p_d8 example4_4k_d6 cornell_800_s512; do run "bench_$c" 600 python3 bench.py --config $c --steps 3 --warmup 1 --no-cpu-baseline; done ;;
+    configs_long) run bench_example3_1080p_d8 600 python3 bench.py --full --config example3_1080p_d8 --steps 100 --warmup 20
+                  run bench_example4_4k_d6 600 python3 bench.py --full --config example4_4k_d6 --steps 20 --warmup 5
+                  run bench_cornell_800_s512 900 python3 bench.py --full --config cornell_800_s512 --steps 2 --warmup 1
+                  run bench_mesh_1080p_d3 600 python3 bench.py --full --config mesh_1080p_d3 --steps 100 --warmup 20 ;;
+    configs) for c in example3_1080p_d8 example4_4k_d6 cornell_800_s512; do run "bench_$c" 600 python3 bench.py --full --config $c --steps 3 --warmup 1 --no-cpu-baseline; done ;;
     pmc_list) run pmc_list 120 rocprofv3 -L ;;
     pmc_sq) run pmc_sq1 600 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU --kernel-trace -d gpurun_out/pmc_sq1 -o bench --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline
             run pmc_sq2 600 rocprofv3 --pmc SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_ACTIVE_INST_SCA SQ_INSTS_BRANCH GRBM_GUI_ACTIVE --kernel-trace -d gpurun_out/pmc_sq2 -o bench --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline ;;
@@ -61,8 +61,8 @@ for step in "$@"; do
     shardprof) run shardprof_${SHARD:-8}_r${SHARD_RANK:-0} 300 rocprofv3 --kernel-trace --memory-copy-trace -d gpurun_out/shardprof_${SHARD:-8}_r${SHARD_RANK:-0} -o s --output-format csv -- python3 bench.py --config ${CONFIG:-example1_1080p_d5} --steps 20 --warmup 2 --no-cpu-baseline --no-secondary --shard-of ${SHARD:-8} --shard-rank ${SHARD_RANK:-0} ;;
     profsync) run profsync 600 rocprofv3 --kernel-trace --stats -d gpurun_out/profsync -o bench --output-format csv -- python3 bench.py --sync --no-cpu-baseline --no-secondary ;;
     profsync_lean) run profsync_lean 600 rocprofv3 --kernel-trace --stats -d gpurun_out/profsync_lean -o bench --output-format csv -- python3 bench.py --sync --option sync_lean=1 --no-cpu-baseline --no-secondary --steps ${STEPS:-45} --warmup 5 ;;
-    driver) run driver 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 ;;
-    rngdev) run bench_rngdev 300 python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --rng device ;;
+    driver) run driver 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 ;;
+    rngdev) run bench_rngdev 300 python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --rng device ;;
     *) echo "unknown step $step"; exit 2 ;;
   esac
 done
