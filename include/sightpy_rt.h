@@ -19,6 +19,10 @@
  *                             (material.py:43, glossy.py:25, refractive.py:24, diffuse.py:25,
  *                              thin_film_interference.py:24, emissive.py:21; the children it
  *                              spawns are traced as in get_raycolor)
+ *   srt_shade_level_inputs <- one level of a built-in Material.get_color whose texture or lights are
+ *                             user subclasses: texture.get_color(hit) (textures/texture.py:14-16) and
+ *                             Light.get_distance / get_irradiance (lights.py:12-22, glossy.py:38-44)
+ *                             run on the host, their values arrive per hit; hybrid scenes only
  *   srt_collider_surface   <- Collider.get_Normal(hit) / Collider.get_uv(hit) / Primitive.get_uv
  *                             (sphere.py:17,54-64, plane.py:34,98-105, cuboid.py:29,142-187,
  *                              triangle.py:85, skybox.py:29)
@@ -47,7 +51,7 @@
 extern "C" {
 #endif
 
-#define SRT_ABI_VERSION 5
+#define SRT_ABI_VERSION 6
 
 /* ---- error codes ------------------------------------------------------------------------ */
 #define SRT_OK 0
@@ -78,6 +82,8 @@ enum {
 #define SRT_MF_ROUGH 1u    /* Glossy: roughness != 0 (specular lobe on) */
 #define SRT_MF_LIGHTMAP 2u /* SkyBox: light_intensity != 0 (lightmap on non-primary rays) */
 #define SRT_MF_NOISE 4u    /* ThinFilm: noise != 0 (thickness jitter from noise texture) */
+#define SRT_MF_HIT_ALBEDO 8u /* Glossy/Diffuse/Emissive: the texture colour arrives per hit (a user texture
+                                subclass; tex = -1): srt_shade_level_inputs only, see srt_hit_inputs */
 
 #define SRT_COLLIDER_PARAMS 48
 #define SRT_MATERIAL_PARAMS 16
@@ -106,6 +112,7 @@ typedef struct srt_collider {
 
 /*
  * Material parameter layout (p[]):
+ *   (SRT_MF_HIT_ALBEDO: 0-2 unused, the colour arrives per hit)
  *   GLOSSY     0-2 solid diffuse colour * diff_coeff (tex < 0), 3 diff_coeff, 4 a = 2/r^2 - 2,
  *              5 a + 2.0, 6 2.0*pi, 7 spec_coeff, 8-10 F0 of the reflection term (scene.n vs n),
  *              11-13 specular F0 for medium 0 (= glossy_f0[m][0]; the specular F0 depends on the
@@ -149,11 +156,14 @@ typedef struct srt_texture {
     double lut[256];
 } srt_texture;
 
-enum { SRT_LIGHT_DIRECTIONAL = 0, SRT_LIGHT_POINT = 1 };
+/* SRT_LIGHT_USER: a user Light subclass.  dir = its get_L() (one direction for every hit), color
+ * unused: get_distance and get_irradiance arrive per hit (srt_hit_inputs).  Its light_local rows are
+ * filled as a directional light's. */
+enum { SRT_LIGHT_DIRECTIONAL = 0, SRT_LIGHT_POINT = 1, SRT_LIGHT_USER = 2 };
 typedef struct srt_light {
     int32_t type;
     int32_t reserved;
-    double dir[3]; /* DirectionalLight.Ldir (normalised by Scene.add_DirectionalLight) */
+    double dir[3]; /* DirectionalLight.Ldir (normalised by Scene.add_DirectionalLight); USER: get_L() */
     double color[3];
     double pos[3]; /* PointLight.pos (kept for the record: shading a Glossy hit under a point light
                       fails with SRT_ERR_NAME, as the reference raises NameError) */
@@ -363,6 +373,30 @@ typedef struct srt_children {
 } srt_children;
 int srt_shade_level(srt_ctx* ctx, const srt_trace_args* args, const int32_t* collider, const double* t,
                     const double* orient, srt_children* children, srt_stats* stats);
+/* srt_shade_level with shading inputs that user code produced at each hit, for a scene holding an
+ * SRT_MF_HIT_ALBEDO material (a user texture subclass on a built-in Glossy / Diffuse / Emissive) or an
+ * SRT_LIGHT_USER light (a user Light subclass).  The built-in work stays on the device (shading
+ * normal, shadow rays, Lambert and Cook-Torrance terms in glossy.py:61-84's order, Fresnel weights,
+ * children); only the values of the user's own methods are read from here, by ray index:
+ *   albedo      texture.get_color(hit) (a Glossy multiplies it by diff_coeff on the device, glossy.py:30)
+ *   light_dist  get_distance(hit.point) of the k-th SRT_LIGHT_USER light (Light_list order): the
+ *               light is seen where the nearest shadow caster along dir is no nearer
+ *   light_irr   get_irradiance(dist_light, NdotL) of that light
+ * `in` NULL, or albedo NULL and n_lights 0: srt_shade_level.  SRT_ERR_ARG when n_lights is not the
+ * scene's count of SRT_LIGHT_USER lights, when the light arrays are NULL with n_lights > 0, or when a
+ * ray's collider has an SRT_MF_HIT_ALBEDO material and albedo is NULL.
+ * Such a scene is shaded only through this entry point (the host-driven recursion of hybrid scenes):
+ * srt_render, srt_render_group, srt_render_prefetch, srt_trace, srt_shade and srt_shade_level on it
+ * fail with SRT_ERR_ARG ("needs per-hit inputs") before any launch. */
+typedef struct srt_hit_inputs {
+    const double* albedo;     /* [3][n] texture.get_color(hit) of ray i, or NULL */
+    int32_t n_lights;         /* SRT_LIGHT_USER lights of the scene, in Light_list order */
+    const double* light_dist; /* [n_lights][n]    get_distance(hit.point) */
+    const double* light_irr;  /* [n_lights][3][n] get_irradiance(dist_light, NdotL) */
+} srt_hit_inputs;
+int srt_shade_level_inputs(srt_ctx* ctx, const srt_trace_args* args, const int32_t* collider, const double* t,
+                           const double* orient, const srt_hit_inputs* in, srt_children* children,
+                           srt_stats* stats);
 /* Collider.get_Normal (N [3][n]) and get_uv (uv [2][n], u then v) at points P [3][n] on the
  * collider; primitive_uv = 1 applies a Cuboid/SkyBox primitive's (4, 3) cross divide
  * (SRT_CF_UV_CROSS, cuboid.py:29-34), 0 returns the collider's own coordinates.  Either output may

@@ -89,6 +89,9 @@ constexpr uint32_t MAT_TRI = 0x80u;   // Triangle colliders intersected one by o
 constexpr uint32_t MAT_NMAP = 0x100u; // a normal-mapped material (shading_normal's texel path)
 constexpr uint32_t MAT_LDS_STACK = 0x200u;   // the BVH traversal stack's first entries in LDS (256-thread blocks)
 constexpr uint32_t MAT_LDS_NARROW = 0x400u;  // ... in k_frame's 64-thread blocks (half as many entries)
+// per-hit shading inputs (HitIn: a user texture's colour, a user light's distance and irradiance);
+// only k_shade_forced's srt_shade_level_inputs instantiations carry it, no variant of the host's tables
+constexpr uint32_t MAT_HITIN = 0x800u;
 constexpr uint32_t MAT_GENERIC = MAT_ALL | MAT_TRI | MAT_NMAP;
 constexpr uint32_t mat_bit(int type) { return 1u << type; }
 // Collider sequence known at compile time (bits 12..31 of a variant's feature mask, 0: the scene's
@@ -1119,10 +1122,25 @@ RT_HD double shadow_nearest(const SceneView& S, int light, d3 O, d3 L, double st
     return best;
 }
 
+// What the user's own methods returned at the hit of ray `pix` of a batch of n rays
+// (srt_hit_inputs; read under MAT_HITIN only): texture.get_color(hit), and per SRT_LIGHT_USER light
+// (Light_list order) get_distance(hit.point) and get_irradiance(dist_light, NdotL)
+struct HitIn {
+    const double* albedo;  // [3][n] or null
+    const double* ldist;   // [user lights][n]
+    const double* lirr;    // [user lights][3][n]
+    int64_t n;
+    int64_t pix;
+};
+RT_HD d3 hitin_albedo(const HitIn* hi) {
+    return d3{hi->albedo[hi->pix], hi->albedo[hi->n + hi->pix], hi->albedo[2 * hi->n + hi->pix]};
+}
+
 // Glossy.get_color (glossy.py:25-110)
 template <uint32_t FEAT = MAT_GENERIC | MAT_BVH, class E>
 RT_HD void shade_glossy(const SceneView& S, const RT_RO srt_collider& c, int mi, const Ray& r, double t, double orient,
-                        E& em, uint32_t& err) {
+                        E& em, uint32_t& err, const HitIn* hi = nullptr) {
+    constexpr bool HITIN = (FEAT & MAT_HITIN) != 0;
     const RT_RO srt_material& m = S.mat[mi];
     RT_T0(tg0);
     d3 P = add(r.o, mul(r.d, t));
@@ -1143,8 +1161,23 @@ RT_HD void shade_glossy(const SceneView& S, const RT_RO srt_collider& c, int mi,
     uint32_t med = meta_medium(r.meta);
     // seelight of the first 32 lights (glossy.py:53-59), tested before the texel is read
     uint32_t see = 0u;
+    [[maybe_unused]] int uk0 = 0;  // (MAT_HITIN) user lights met so far
     for (int l = 0; l < S.nlights && l < 32; ++l) {
         const RT_RO srt_light& Lt = S.lights[l];
+        if constexpr (HITIN) {
+            // a user Light: seelight = light_nearest >= get_distance(hit.point) (glossy.py:57)
+            if (Lt.type == SRT_LIGHT_USER) {
+                const double stop = hi->ldist[(int64_t)uk0 * hi->n + hi->pix];
+                ++uk0;
+                if (S.nshadow > 0) {
+                    if (shadow_nearest<FEAT>(S, l, nudged, ld3(Lt.dir), stop) >= stop) see |= 1u << l;
+                    em.shadow(1);
+                } else {
+                    see |= 1u << l;
+                }
+                continue;
+            }
+        }
         if (Lt.type != SRT_LIGHT_DIRECTIONAL) continue;
 #ifndef RT_ABL_SHADOW  // (diagnostic build only: time without the shadow test)
         if (S.nshadow > 0) {
@@ -1159,20 +1192,35 @@ RT_HD void shade_glossy(const SceneView& S, const RT_RO srt_collider& c, int mi,
             see |= 1u << l;
         }
     }
-    const d3 diff = m.tex >= 0 ? mul(word_rgb(S, m.tex, tw), m.p[3]) : ld3(m.p);
+    d3 diff = m.tex >= 0 ? mul(word_rgb(S, m.tex, tw), m.p[3]) : ld3(m.p);
+    if constexpr (HITIN) {
+        // a user texture's colour times diff_coeff (glossy.py:30), where the texel path multiplies
+        if (m.flags & SRT_MF_HIT_ALBEDO) diff = mul(hitin_albedo(hi), m.p[3]);
+    }
     d3 color = mul(ld3(S.ambient), diff);
+    [[maybe_unused]] int uk = 0;
     for (int l = 0; l < S.nlights; ++l) {
         const RT_RO srt_light& Lt = S.lights[l];
-        if (Lt.type != SRT_LIGHT_DIRECTIONAL) {
+        bool user = false;
+        if constexpr (HITIN) user = Lt.type == SRT_LIGHT_USER;
+        if (Lt.type != SRT_LIGHT_DIRECTIONAL && !user) {
             // PointLight.get_L reads the undefined names M and dist_light (lights.py:30-31): the
             // reference's render raises NameError at the first Glossy hit, so does this one
             err |= ERR_NAME;
             continue;
         }
         const d3 L = ld3(Lt.dir);
-        const double dist = SKYBOX_DISTANCE;
+        double dist = SKYBOX_DISTANCE;
         double NdotL = np_max(dot(N, L), 0.0);
-        const d3 lv = mul(ld3(Lt.color), NdotL);
+        d3 lv = mul(ld3(Lt.color), NdotL);
+        if constexpr (HITIN) {
+            if (user) {  // get_distance(hit.point), get_irradiance(dist_light, NdotL) as the user's code gave them
+                dist = hi->ldist[(int64_t)uk * hi->n + hi->pix];
+                const double* ir = hi->lirr + (int64_t)uk * 3 * hi->n + hi->pix;
+                lv = d3{ir[0], ir[hi->n], ir[2 * hi->n]};
+                ++uk;
+            }
+        }
         d3 H = normalize(add(L, V));
         double seelight = 1.0;
         if (l < 32) {
@@ -1375,10 +1423,16 @@ RT_HD d3 sky_color(const SceneView& S, const Ray& r, uint32_t w0, uint32_t w1) {
 }
 
 // Emissive.get_color (emissive.py:21-23)
-template <class E>
+template <uint32_t FEAT = 0u, class E>
 RT_HD void shade_emissive(const SceneView& S, const RT_RO srt_collider& c, int mi, const Ray& r, double t, E& em,
-                          uint32_t& err) {
+                          uint32_t& err, const HitIn* hi = nullptr) {
     const RT_RO srt_material& m = S.mat[mi];
+    if constexpr ((FEAT & MAT_HITIN) != 0) {
+        if (m.flags & SRT_MF_HIT_ALBEDO) {
+            em.local(hitin_albedo(hi));
+            return;
+        }
+    }
     if (m.tex >= 0) {
         double u, v;
         d3 P = add(r.o, mul(r.d, t));
@@ -1392,7 +1446,7 @@ RT_HD void shade_emissive(const SceneView& S, const RT_RO srt_collider& c, int m
 // Diffuse.get_color (diffuse.py:25-124): no local colour; the children carry the estimate
 template <uint32_t FEAT = MAT_GENERIC | MAT_BVH, class E>
 RT_HD void shade_diffuse(const SceneView& S, const RT_RO srt_collider& c, int mi, const Ray& r, double t, double orient,
-                         E& em, uint32_t& err) {
+                         E& em, uint32_t& err, const HitIn* hi = nullptr) {
     uint32_t dfl = meta_diffuse(r.meta);
     if (dfl >= 2) return;
     const RT_RO srt_material& m = S.mat[mi];
@@ -1405,6 +1459,9 @@ RT_HD void shade_diffuse(const SceneView& S, const RT_RO srt_collider& c, int mi
         diff = tex_rgb(S, m.tex, u, v, err);
     } else {
         diff = ld3(m.p);
+    }
+    if constexpr ((FEAT & MAT_HITIN) != 0) {
+        if (m.flags & SRT_MF_HIT_ALBEDO) diff = hitin_albedo(hi);
     }
     DiffuseGen g;
     g.count = (dfl < 1) ? m.ival : 1;

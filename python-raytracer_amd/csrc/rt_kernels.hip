@@ -128,6 +128,15 @@ struct TraceParams {
     // them) of the fused paths' depth loop, or null (counting off)
     unsigned long long* lane_stats;
 };
+// k_shade_forced_inputs (srt_shade_level_inputs): what the user's texture / Light methods returned per
+// ray (index = pix, batch of npix), or null.  A kernel argument of its own: the kernels that take
+// TraceParams alone keep their argument block (several copy it to scratch: 24 bytes more there grew
+// their scratch size).
+struct HitPtrs {
+    const double* albedo;  // [3][npix]
+    const double* ldist;   // [user lights][npix]
+    const double* lirr;    // [user lights][3][npix]
+};
 // kernel argument: host and device passes must agree on the layout (catches address-space pointer
 // size differences, see SceneView)
 static_assert(sizeof(TraceParams) == TRACE_PARAMS_BYTES, "TraceParams layout");
@@ -429,7 +438,7 @@ struct em_in_place<Em, std::void_t<decltype(Em::kInPlace)>> : std::bool_constant
 // is round 0's, tied colliders get copies with rounds 1, 2, ...
 template <uint32_t MATS, class Em, bool FORCED = false>
 __device__ __forceinline__ void trace_one(const TraceParams& P, Ray& r, bool active, uint32_t& err, int32_t* hit_slot,
-                                          const Em& em0) {
+                                          const Em& em0, const HitPtrs* hp = nullptr) {
     const SceneView& S = P.S;
     double t = FARAWAY, o = FARAWAY;
     bool ties = false;
@@ -469,6 +478,13 @@ __device__ __forceinline__ void trace_one(const TraceParams& P, Ray& r, bool act
     // copy of the shaders per kernel (a separate tie loop held a second one: the kernels waited on
     // ~10 % of their wave cycles in SQ_WAIT_INST_ANY; round 6: issue stalls, the i-cache misses 0.004 %).
     RT_T0(tw0);
+    // srt_shade_level_inputs: the per-hit inputs of this ray
+    [[maybe_unused]] HitIn hin{};
+    const HitIn* hi = nullptr;
+    if constexpr (FORCED && (MATS & MAT_HITIN) != 0) {
+        hin = HitIn{hp->albedo, hp->ldist, hp->lirr, P.npix, (int64_t)r.pix};
+        hi = &hin;
+    }
     // a SkyBox / Panorama hit without a tie: its texel words fetched now, its colour added after the
     // waterfall of the other colliders (the load latency overlaps their shading; fixed-point sums do
     // not depend on the order of the terms)
@@ -498,7 +514,7 @@ __device__ __forceinline__ void trace_one(const TraceParams& P, Ray& r, bool act
             if (rnd) em.round = rnd;
             switch (S.mat[m].type) {
                 case SRT_GLOSSY:
-                    if (MATS & mat_bit(SRT_GLOSSY)) shade_glossy<MATS>(S, c, m, r, t, co, em, err);
+                    if (MATS & mat_bit(SRT_GLOSSY)) shade_glossy<MATS>(S, c, m, r, t, co, em, err, hi);
                     break;
                 case SRT_REFRACTIVE:
                     if (MATS & mat_bit(SRT_REFRACTIVE))
@@ -508,10 +524,10 @@ __device__ __forceinline__ void trace_one(const TraceParams& P, Ray& r, bool act
                     if (MATS & mat_bit(SRT_THINFILM)) shade_thinfilm<MATS>(S, c, m, r, t, co, em, err);
                     break;
                 case SRT_DIFFUSE:
-                    if (MATS & mat_bit(SRT_DIFFUSE)) shade_diffuse<MATS>(S, c, m, r, t, co, em, err);
+                    if (MATS & mat_bit(SRT_DIFFUSE)) shade_diffuse<MATS>(S, c, m, r, t, co, em, err, hi);
                     break;
                 case SRT_EMISSIVE:
-                    if (MATS & mat_bit(SRT_EMISSIVE)) shade_emissive(S, c, m, r, t, em, err);
+                    if (MATS & mat_bit(SRT_EMISSIVE)) shade_emissive<MATS>(S, c, m, r, t, em, err, hi);
                     break;
                 default:
                     if (MATS & mat_bit(SRT_SKY)) shade_sky(S, c, m, r, t, em, err);
@@ -761,8 +777,7 @@ __global__ __launch_bounds__(BLOCK, OCC) void k_trace(TraceParams P0) {
 // srt_shade's first depth: each queued ray shaded at the caller's hit (Material.get_color,
 // material.py:42-44), its children appended for the ordinary k_trace depths
 template <uint32_t MATS>
-__global__ __launch_bounds__(BLOCK) void k_shade_forced(TraceParams P0) {
-    const TraceParams& P = P0;
+__device__ __forceinline__ void shade_forced_body(const TraceParams& P, const HitPtrs* hp) {
     const uint32_t shard = blockIdx.x % NSHARD;
     const int64_t n = min((int64_t)P.cnt_in[shard], P.seg);
     const int64_t blk = blockIdx.x / NSHARD, nblk = gridDim.x / NSHARD;
@@ -781,10 +796,20 @@ __global__ __launch_bounds__(BLOCK) void k_shade_forced(TraceParams P0) {
             r.o = r.d = r.w = d3{0.0, 0.0, 0.0};
             r.pix = 0; r.meta = 0; r.path = 0;
         }
-        trace_one<MATS, GpuEmit, true>(P, r, active, err, nullptr, GpuEmit{P, r, shard, 0u, &shadow, nullptr});
+        trace_one<MATS, GpuEmit, true>(P, r, active, err, nullptr, GpuEmit{P, r, shard, 0u, &shadow, nullptr}, hp);
     }
     if (err) atomicOr(&P.flags[0], err);
     if (shadow) atomicAdd(P.shadow, (unsigned long long)shadow);
+}
+template <uint32_t MATS>
+__global__ __launch_bounds__(BLOCK) void k_shade_forced(TraceParams P0) {
+    shade_forced_body<MATS>(P0, nullptr);
+}
+// srt_shade_level_inputs' first depth: k_shade_forced with the per-hit shading inputs (MAT_HITIN)
+template <uint32_t MATS>
+__global__ __launch_bounds__(BLOCK) void k_shade_forced_inputs(TraceParams P0, HitPtrs H) {
+    static_assert((MATS & MAT_HITIN) != 0, "the per-hit inputs are read under MAT_HITIN");
+    shade_forced_body<MATS>(P0, &H);
 }
 
 // ---- the frame kernel ----------------------------------------------------------------------
@@ -1606,6 +1631,11 @@ struct srt_ctx {
     uint32_t mats = 0;  // material types present (selects the kernel variant)
     uint32_t seq = 0;   // the scene's collider sequence (rt_device.h seq_encode; 0: none, or option collider_seq 0)
     bool seq_on = true;  // option "collider_seq": kernels specialised to the scene's collider sequence when built
+    // per-hit shading inputs (srt_shade_level_inputs): colliders whose material has SRT_MF_HIT_ALBEDO,
+    // the scene's SRT_LIGHT_USER lights; a scene with either is shaded through that entry point only
+    std::vector<uint8_t> col_hit_albedo;
+    int n_user_lights = 0;
+    bool needs_inputs = false;
     std::vector<void*> scene_bufs;
     // texel pool (outside scene_bufs: survives re-uploads with the same texel_key)
     uint8_t* texels = nullptr;
@@ -1891,6 +1921,16 @@ int ptr_kind(const void* p) {
         if (_r != ncclSuccess)                                                                  \
             return fail(SRT_ERR_HIP, std::string(#expr) + ": " + ncclGetErrorString(_r));      \
     } while (0)
+
+// A scene with an SRT_MF_HIT_ALBEDO material or an SRT_LIGHT_USER light is shaded only by
+// srt_shade_level_inputs (the hot kernels have no path for it): every other entry point refuses it
+// before any launch
+int refuse_inputs_scene(const char* who) {
+    char msg[256];
+    snprintf(msg, sizeof(msg), "%s: the scene needs per-hit inputs (an SRT_MF_HIT_ALBEDO material or an "
+             "SRT_LIGHT_USER light): it is shaded through srt_shade_level_inputs only", who);
+    return fail(SRT_ERR_ARG, msg);
+}
 
 int check_flags(uint32_t f0) {
     if (f0 & ERR_INDEX)
@@ -2666,7 +2706,13 @@ int srt_upload_scene(srt_ctx* c, const srt_scene_desc* d) {
         if ((m.type == SRT_SKY && m.tex < 0) || (m.type == SRT_THINFILM && (m.tex_aux0 < 0 || m.tex_aux1 < 0)))
             return fail(SRT_ERR_ARG, "material is missing a required texture");
         if (m.type == SRT_DIFFUSE && (m.ival < 1 || m.ival > 255)) return fail(SRT_ERR_ARG, "diffuse_rays must be 1..255");
+        if ((m.flags & SRT_MF_HIT_ALBEDO) &&
+            ((m.type != SRT_GLOSSY && m.type != SRT_DIFFUSE && m.type != SRT_EMISSIVE) || m.tex >= 0))
+            return fail(SRT_ERR_ARG, "SRT_MF_HIT_ALBEDO: a Glossy / Diffuse / Emissive material with tex = -1");
     }
+    for (int i = 0; i < d->n_lights; ++i)
+        if (d->lights[i].type < SRT_LIGHT_DIRECTIONAL || d->lights[i].type > SRT_LIGHT_USER)
+            return fail(SRT_ERR_ARG, "bad light type");
     HIP_TRY(hipSetDevice(c->device));
     int rc0 = finish_async(c, nullptr);  // frames in flight read the scene tables freed below
     if (rc0) return rc0;
@@ -2824,6 +2870,16 @@ int srt_upload_scene(srt_ctx* c, const srt_scene_desc* d) {
         for (int i = 0; i < d->n_colliders; ++i) types[i] = d->colliders[i].type;
         c->seq = seq_encode(types, d->n_colliders);
     }
+    c->col_hit_albedo.assign((size_t)std::max(0, d->n_colliders), 0);
+    c->n_user_lights = 0;
+    c->needs_inputs = false;
+    for (int i = 0; i < d->n_colliders; ++i)
+        if (d->materials[d->colliders[i].material].flags & SRT_MF_HIT_ALBEDO) c->col_hit_albedo[i] = 1;
+    for (int i = 0; i < d->n_materials; ++i)
+        if (d->materials[i].flags & SRT_MF_HIT_ALBEDO) c->needs_inputs = true;
+    for (int i = 0; i < d->n_lights; ++i)
+        if (d->lights[i].type == SRT_LIGHT_USER) c->n_user_lights++;
+    if (c->n_user_lights > 0) c->needs_inputs = true;
     c->chain_ok = true;
     c->hint_key[0] = -1;  // ray counts of another scene are no plan for this one
     c->has_scene = true;
@@ -2842,6 +2898,7 @@ int render_impl(srt_ctx* c, const srt_camera* cam, const srt_render_args* a, srt
     const srt_ctx::MtPrefetch pf_in = c->pf;  // (a prefetch is used by the next render only)
     c->pf.valid = false;
     if (!prefetch && !c->has_scene) return fail(SRT_ERR_NOSCENE, "no scene uploaded");
+    if (c->has_scene && c->needs_inputs) return refuse_inputs_scene(prefetch ? "srt_render_prefetch" : "srt_render");
     if (a->flags & ~(SRT_RENDER_ASYNC | SRT_RENDER_SHARDED | SRT_RENDER_GATHER_RGB | SRT_RENDER_RGB_ROWS |
                      SRT_RENDER_RGB_LOCAL | SRT_RENDER_RGBX))
         return fail(SRT_ERR_ARG, "unknown render flag");
@@ -3555,12 +3612,15 @@ int srt_stream(srt_ctx* c, void** stream) {
 namespace {
 // get_raycolor (srt_trace) or Material.get_color at given hits (srt_shade: fid/ft/fo non-null)
 // kids (srt_shade_level): shade the first depth only and hand its children back instead of tracing them
+// in (srt_shade_level_inputs): the per-hit shading inputs of a scene that needs them
 int trace_impl(srt_ctx* c, const srt_trace_args* a, const int32_t* fid, const double* ft, const double* fo,
-               srt_stats* st, srt_children* kids = nullptr) {
+               srt_stats* st, srt_children* kids = nullptr, const srt_hit_inputs* in = nullptr,
+               const char* who = "srt_trace") {
     auto t_start = std::chrono::steady_clock::now();
     if (!c || !a || !a->origin || !a->dir || !a->out_rgb) return fail(SRT_ERR_ARG, "null argument");
     c->pf.valid = false;  // (slot 0's buffers are reused here)
     if (!c->has_scene) return fail(SRT_ERR_NOSCENE, "no scene uploaded");
+    if (c->needs_inputs && !in) return refuse_inputs_scene(who);
     if (a->depth < 0 || a->depth > 200 || a->diffuse_reflections < 0) return fail(SRT_ERR_ARG, "bad depth");
     if (a->n <= 0) return SRT_OK;
     if (a->n >= ((int64_t)1 << 31)) return fail(SRT_ERR_ARG, "batch too large");
@@ -3579,6 +3639,18 @@ int trace_impl(srt_ctx* c, const srt_trace_args* a, const int32_t* fid, const do
     HIP_TRY(hipMemcpyAsync(O, a->origin, (size_t)3 * n * 8, hipMemcpyDefault, c->f->stream));
     HIP_TRY(hipMemcpyAsync(D, a->dir, (size_t)3 * n * 8, hipMemcpyDefault, c->f->stream));
     if (med) HIP_TRY(hipMemcpyAsync(med, a->medium, (size_t)n * 4, hipMemcpyDefault, c->f->stream));
+    // the user's per-hit values, copied in with the other per-call buffers
+    double *dalb = nullptr, *dldist = nullptr, *dlirr = nullptr;
+    if (in && in->albedo) {
+        HIP_TRY(bufs.alloc(&dalb, 3 * n));
+        HIP_TRY(hipMemcpyAsync(dalb, in->albedo, (size_t)3 * n * 8, hipMemcpyDefault, c->f->stream));
+    }
+    if (in && in->n_lights > 0) {
+        HIP_TRY(bufs.alloc(&dldist, (int64_t)in->n_lights * n));
+        HIP_TRY(bufs.alloc(&dlirr, (int64_t)in->n_lights * 3 * n));
+        HIP_TRY(hipMemcpyAsync(dldist, in->light_dist, (size_t)in->n_lights * n * 8, hipMemcpyDefault, c->f->stream));
+        HIP_TRY(hipMemcpyAsync(dlirr, in->light_irr, (size_t)in->n_lights * 3 * n * 8, hipMemcpyDefault, c->f->stream));
+    }
     int32_t* dfid = nullptr;
     double *dft = nullptr, *dfo = nullptr;
     if (fid) {
@@ -3627,8 +3699,15 @@ int trace_impl(srt_ctx* c, const srt_trace_args* a, const int32_t* fid, const do
                 P.force_id = dfid;
                 P.force_t = dft;
                 P.force_o = dfo;
-                hipLaunchKernelGGL((c->mats & MAT_BVH) ? k_shade_forced<MAT_GENERIC | MAT_BVH> : k_shade_forced<MAT_GENERIC>,
-                                   dim3(trace_grid(c)), dim3(BLOCK), lut_bytes(c), c->f->stream, P);
+                if (in) {
+                    const HitPtrs H{dalb, dldist, dlirr};
+                    hipLaunchKernelGGL((c->mats & MAT_BVH) ? k_shade_forced_inputs<MAT_GENERIC | MAT_BVH | MAT_HITIN>
+                                                           : k_shade_forced_inputs<MAT_GENERIC | MAT_HITIN>,
+                                       dim3(trace_grid(c)), dim3(BLOCK), lut_bytes(c), c->f->stream, P, H);
+                } else {
+                    hipLaunchKernelGGL((c->mats & MAT_BVH) ? k_shade_forced<MAT_GENERIC | MAT_BVH> : k_shade_forced<MAT_GENERIC>,
+                                       dim3(trace_grid(c)), dim3(BLOCK), lut_bytes(c), c->f->stream, P);
+                }
                 P.force_id = nullptr;
                 P.force_t = P.force_o = nullptr;
             } else {
@@ -3736,7 +3815,7 @@ int srt_trace(srt_ctx* c, const srt_trace_args* a, srt_stats* st) {
 int srt_shade(srt_ctx* c, const srt_trace_args* a, const int32_t* collider, const double* t, const double* orient,
               srt_stats* st) {
     if (!collider || !t || !orient) return fail(SRT_ERR_ARG, "null hit arrays");
-    return trace_impl(c, a, collider, t, orient, st);
+    return trace_impl(c, a, collider, t, orient, st, nullptr, nullptr, "srt_shade");
 }
 
 int srt_shade_level(srt_ctx* c, const srt_trace_args* a, const int32_t* collider, const double* t, const double* orient,
@@ -3746,7 +3825,48 @@ int srt_shade_level(srt_ctx* c, const srt_trace_args* a, const int32_t* collider
     if (kids->cap < 0 || (kids->cap > 0 && (!kids->origin || !kids->dir || !kids->weight || !kids->parent ||
                                             !kids->medium || !kids->depth || !kids->diffuse_reflections)))
         return fail(SRT_ERR_ARG, "srt_children arrays");
-    return trace_impl(c, a, collider, t, orient, st, kids);
+    return trace_impl(c, a, collider, t, orient, st, kids, nullptr, "srt_shade_level");
+}
+
+int srt_shade_level_inputs(srt_ctx* c, const srt_trace_args* a, const int32_t* collider, const double* t,
+                           const double* orient, const srt_hit_inputs* in, srt_children* kids, srt_stats* st) {
+    if (!in || (!in->albedo && in->n_lights == 0)) {
+        // nothing per hit: srt_shade_level (which refuses a scene that needs inputs; a flagged
+        // material or a user light then names the missing array below)
+        if (!c || !c->has_scene || !c->needs_inputs) return srt_shade_level(c, a, collider, t, orient, kids, st);
+    }
+    if (!c || !a) return fail(SRT_ERR_ARG, "null argument");
+    if (!collider || !t || !orient || !kids) return fail(SRT_ERR_ARG, "null hit / children arrays");
+    kids->n = 0;
+    if (kids->cap < 0 || (kids->cap > 0 && (!kids->origin || !kids->dir || !kids->weight || !kids->parent ||
+                                            !kids->medium || !kids->depth || !kids->diffuse_reflections)))
+        return fail(SRT_ERR_ARG, "srt_children arrays");
+    if (!c->has_scene) return fail(SRT_ERR_NOSCENE, "no scene uploaded");
+    const srt_hit_inputs none{nullptr, 0, nullptr, nullptr};
+    if (!in) in = &none;
+    char msg[256];
+    if (in->n_lights != c->n_user_lights) {
+        snprintf(msg, sizeof(msg), "srt_hit_inputs.n_lights is %d, the scene holds %d SRT_LIGHT_USER lights",
+                 (int)in->n_lights, c->n_user_lights);
+        return fail(SRT_ERR_ARG, msg);
+    }
+    if (in->n_lights > 0 && (!in->light_dist || !in->light_irr))
+        return fail(SRT_ERR_ARG, "srt_hit_inputs.light_dist / light_irr are NULL while n_lights > 0");
+    if (!in->albedo && a->n > 0 && a->n < ((int64_t)1 << 31)) {
+        // (the hit's collider decides whether a colour is read: checked here, the kernel reads unguarded)
+        std::vector<int32_t> ids((size_t)a->n);
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipMemcpy(ids.data(), collider, (size_t)a->n * 4, hipMemcpyDefault));
+        for (int64_t i = 0; i < a->n; ++i) {
+            const int32_t id = ids[(size_t)i];
+            if (id >= 0 && id < (int32_t)c->col_hit_albedo.size() && c->col_hit_albedo[(size_t)id]) {
+                snprintf(msg, sizeof(msg), "srt_hit_inputs.albedo is NULL, but ray %lld hits collider %d whose "
+                         "material has SRT_MF_HIT_ALBEDO", (long long)i, (int)id);
+                return fail(SRT_ERR_ARG, msg);
+            }
+        }
+    }
+    return trace_impl(c, a, collider, t, orient, st, kids, in, "srt_shade_level_inputs");
 }
 
 int srt_nearest(srt_ctx* c, const double* O, const double* D, int64_t n, double* t, int32_t* id, double* orient) {
@@ -4061,6 +4181,8 @@ int srt_render_group(srt_ctx** ctxs, int n, const srt_camera* cam, const srt_ren
         if (!ctxs[q] || ctxs[q]->nranks != n || ctxs[q]->rank != q)
             return fail(SRT_ERR_ARG, "contexts must be the ranks 0..n-1 of one srt_comm_init_all group");
     for (int q = 0; q < n; ++q) ctxs[q]->pf.valid = false;
+    for (int q = 0; q < n; ++q)
+        if (ctxs[q]->has_scene && ctxs[q]->needs_inputs) return refuse_inputs_scene("srt_render_group");
     if (a->jitter) return fail(SRT_ERR_ARG, "a group frame draws its jitter on the devices (mt or Philox)");
     if (a->out_hit_id) return fail(SRT_ERR_ARG, "hit ids of a sharded frame are not gathered");
     if (a->flags & ~(SRT_RENDER_ASYNC | SRT_RENDER_RGB_ROWS | SRT_RENDER_RGB_LOCAL))

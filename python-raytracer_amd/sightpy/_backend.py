@@ -13,7 +13,7 @@ from . import _native as N
 from ._lower import lower_scene, camera_desc, collider_record
 from .utils.vector3 import vec3
 
-_STATE = {"lib": None, "ctx": None, "device": None, "scene_sig": {}, "buffers": {}, "pinned": {}, "group": None}
+_STATE = {"lib": None, "ctx": None, "device": None, "scene_sig": {}, "scene_inputs": {}, "buffers": {}, "pinned": {}, "group": None}
 
 
 class RenderResult:
@@ -125,6 +125,10 @@ def upload(scene, extra_media=(), force=False, ctx=None):
         _STATE["scene_sig"].pop(key, None)
         N.check(lib, lib.srt_upload_scene(ctx, ctypes.byref(L.desc())))
         _STATE["scene_sig"][key] = sig
+        # a scene shaded with per-hit inputs (a user texture / Light, _hybrid.py): the library refuses
+        # every whole-frame entry point on it, srt_render_prefetch included
+        _STATE["scene_inputs"][key] = bool((L.materials["flags"] & N.MF_HIT_ALBEDO).any()
+                                           or (L.lights["type"] == N.LIGHT_USER).any())
     return L
 
 
@@ -323,7 +327,9 @@ def render_scene(scene, spp, jitter=None, seed=None, batch_size=None, rows=None,
         state = N.MtState.from_numpy()
         a.mt = ctypes.pointer(state)
     a.flags = (0 if want_rgb else N.RENDER_RGB_LOCAL) | (N.RENDER_RGBX if rgbx else 0)
-    if mt and prefetch and rows_arr is None and nrows == H:
+    # (the prefetch runs before this frame's scene replaces the resident one: not while that one is a
+    # per-hit-inputs scene, on which the library refuses it)
+    if mt and prefetch and rows_arr is None and nrows == H and not _STATE["scene_inputs"].get(ctx.value):
         N.check(lib, lib.srt_render_prefetch(ctx, ctypes.byref(cd), ctypes.byref(a)))
     upload(scene)
     rgb = np.empty((3, npix)) if want_rgb else None

@@ -1,6 +1,8 @@
-"""Scenes holding user subclasses of `Collider` or `Material`: the reference's duck-typed plugin
-dispatch (`ray.py:122-148` calls `intersect` and `get_color` on whatever the lists hold; contracts
-at `geometry/collider.py:12-14` and `materials/material.py:42-44`).
+"""Scenes holding user subclasses of `Collider`, `Material`, `texture` or `Light`: the reference's
+duck-typed plugin dispatch (`ray.py:122-148` calls `intersect` and `get_color` on whatever the lists
+hold, `glossy.py:30,38-44` the texture's `get_color(hit)` and the lights' `get_L` / `get_distance` /
+`get_irradiance`; contracts at `geometry/collider.py:12-14`, `materials/material.py:42-44`,
+`textures/texture.py:14-16` and `lights.py:12-22`).
 
 A user class's Python methods cannot run inside a kernel, so such a scene is traced by the
 reference's own recursion structure, driven from the host one batch level at a time, with every
@@ -14,12 +16,22 @@ step the device can take on the device:
     `get_raycolor` comes back here); a built-in material on a built-in collider shades its rays on
     the device one level deep (`srt_shade_level`: the colour it adds before its children, and the
     children with the factor their colour is multiplied by), and the children are traced by this
-    same recursion, so they can hit user colliders.
+    same recursion, so they can hit user colliders;
+  * a user texture on a built-in Glossy / Diffuse / Emissive, a user Light in Light_list: the
+    material is still shaded on the device, one level at a time (`srt_shade_level_inputs`: shading
+    normal, shadow rays, Lambert and Cook-Torrance terms, Fresnel weights, children).  Only the
+    user's own methods run here, on the level's batch, as the reference runs them:
+    `texture.get_color(hit)` (its `hit.get_uv()` is a device entry point), and for each user light
+    `get_distance(hit.point)` and `get_irradiance(dist_light, NdotL)` with `NdotL =
+    maximum(N.dot(L), 0)` of the material's device normal (glossy.py:41; that dot product is the
+    callback's argument, nothing else of the material is computed on the host).  Their values go to
+    the device per hit.  `get_L()` must be one direction (a vec3 of scalars): a per-ray light
+    direction is refused.  Per-hit inputs exist only in this host-driven path.
 
 Scenes made only of built-in classes never come here: they render in the device kernels whole.
 
 What the device cannot do for a user class is refused (NotImplementedError) rather than computed
-on the CPU: a built-in material on a user collider (the device shaders take the surface from the
+on the CPU, with or without user textures and lights in the scene: a built-in material on a user collider (the device shaders take the surface from the
 built-in colliders' device code), and a user collider casting shadows (`shadow=True`) in a scene
 with built-in Glossy materials (their shadow rays, glossy.py:54-67, are traced on the device
 against the device's colliders; a built-in collider with a user material is one of them).  Monte-Carlo materials (Diffuse, `mc=True` Refractive) shaded on
@@ -33,7 +45,7 @@ import numpy as np
 from .utils.constants import FARAWAY
 from .utils.vector3 import vec3, rgb, extract
 
-__all__ = ["device_collider", "device_material", "on_device", "is_hybrid", "raycolor", "shade_level",
+__all__ = ["device_collider", "device_material", "device_texture", "device_light", "on_device", "is_hybrid", "raycolor", "shade_level",
            "render_linear", "nearest_distance"]
 
 _SURFACE_METHODS = ("intersect", "get_Normal", "get_uv")
@@ -72,18 +84,70 @@ def device_material(m):
     return isinstance(m, _builtin_materials()) and type(m).get_color is Material.get_color
 
 
+def device_texture(t):
+    """A `solid_color` or `image` (or a subclass of one that keeps its get_color): the device reads
+    its colour from the scene tables."""
+    from .textures.texture import solid_color, image
+
+    for base in (solid_color, image):
+        if isinstance(t, base):
+            return type(t).get_color is base.get_color
+    return False
+
+
+_LIGHT_METHODS = ("get_L", "get_distance", "get_irradiance")
+
+
+def device_light(l):
+    """A `DirectionalLight` or `PointLight` (or a subclass of one that keeps get_L / get_distance /
+    get_irradiance): a record of the device's light table."""
+    from .lights import DirectionalLight, PointLight
+
+    for base in (DirectionalLight, PointLight):
+        if isinstance(l, base):
+            t = type(l)
+            return all(getattr(t, m, None) is getattr(base, m, None) for m in _LIGHT_METHODS)
+    return False
+
+
+def material_texture(m):
+    """The colour texture of a built-in Glossy / Diffuse / Emissive, else None."""
+    from .materials import Glossy, Diffuse, Emissive
+
+    if isinstance(m, (Glossy, Diffuse)):
+        return getattr(m, "diff_texture", None)
+    if isinstance(m, Emissive):
+        return getattr(m, "texture_color", None)
+    return None
+
+
+def user_texture(m):
+    """The user texture a built-in material holds (its colour arrives per hit), else None."""
+    if not device_material(m):
+        return None
+    t = material_texture(m)
+    return t if t is not None and not device_texture(t) else None
+
+
+def needs_inputs(scene):
+    """Whether a built-in material holds a user texture or Light_list a user Light."""
+    return (any(user_texture(c.assigned_primitive.material) is not None for c in scene.collider_list)
+            or not all(device_light(l) for l in scene.Light_list))
+
+
 def on_device(c):
     """The collider and its material both lower to the device tables."""
     return device_collider(c) and device_material(c.assigned_primitive.material)
 
 
 def is_hybrid(scene):
-    """Whether `scene` holds a user Collider / Material subclass (cached per collider list)."""
-    key = (id(scene.collider_list), len(scene.collider_list))
+    """Whether `scene` holds a user Collider / Material / texture / Light subclass (cached per
+    collider list and light list)."""
+    key = (id(scene.collider_list), len(scene.collider_list), tuple(id(l) for l in scene.Light_list))
     cached = getattr(scene, "_hybrid_key", None)
     if cached is not None and cached[0] == key:
         return cached[1]
-    res = not all(on_device(c) for c in scene.collider_list)
+    res = not all(on_device(c) for c in scene.collider_list) or needs_inputs(scene)
     if res:
         _check(scene)
     scene._hybrid_key = (key, res)
@@ -144,9 +208,42 @@ def raycolor(ray, scene):
     return color
 
 
+def _rows(v, n):
+    """A user method's result (a scalar, or a vec3 of scalars or arrays) as float64 (3, n)."""
+    comps = (v.x, v.y, v.z) if hasattr(v, "x") else (v, v, v)
+    return np.ascontiguousarray(np.stack([np.broadcast_to(np.asarray(c, dtype=np.float64).reshape(-1)
+                                                          if np.ndim(c) else np.asarray(c, dtype=np.float64), (n,))
+                                          for c in comps]))
+
+
+def hit_inputs(scene, material, hit, n):
+    """What the user's texture / Light methods return at `hit` (hit.point set), for
+    srt_shade_level_inputs: (albedo (3, n) or None, light_dist (k, n), light_irr (k, 3, n)) over the
+    scene's k user lights in Light_list order.  The lights are consulted for a Glossy only, as in the
+    reference (glossy.py:37-44); other materials never read their rows."""
+    from .materials import Glossy
+
+    tex = user_texture(material)
+    albedo = _rows(tex.get_color(hit), n) if tex is not None else None
+    users = [l for l in scene.Light_list if not device_light(l)]
+    dist = np.zeros((len(users), n))
+    irr = np.zeros((len(users), 3, n))
+    if users and isinstance(material, Glossy):
+        N = material.get_Normal(hit)
+        if not hasattr(N, "x"):
+            N = vec3(N[0], N[1], N[2])
+        for k, l in enumerate(users):
+            NdotL = np.maximum(N.dot(l.get_L()), 0.0)
+            d = l.get_distance(hit.point)
+            dist[k] = np.broadcast_to(np.asarray(d, dtype=np.float64).reshape(-1) if np.ndim(d) else d, (n,))
+            irr[k] = _rows(l.get_irradiance(d, NdotL), n)
+    return albedo, dist, irr
+
+
 def shade_level(scene, material, ray, hit):
     """A built-in material's get_color in a scene with user classes: its own colour from the
-    device (srt_shade_level), plus each child's colour (this recursion) times its factor."""
+    device (srt_shade_level; srt_shade_level_inputs when the scene holds a user texture or Light,
+    whose methods run here on this batch), plus each child's colour (this recursion) times its factor."""
     import ctypes
 
     from . import _backend as B, _native as N
@@ -170,6 +267,13 @@ def shade_level(scene, material, ray, hit):
     ids = np.full(n, dev, dtype=np.int32)
     t = np.ascontiguousarray(np.broadcast_to(np.asarray(hit.distance, dtype=np.float64), (n,)))
     o = np.ascontiguousarray(np.broadcast_to(np.asarray(hit.orientation, dtype=np.float64), (n,)))
+    inputs = None
+    if needs_inputs(scene):
+        albedo, ldist, lirr = hit_inputs(scene, material, hit, n)
+        inputs = N.HitInputs()
+        inputs.albedo = N.ptr(albedo)
+        inputs.n_lights = len(ldist)
+        inputs.light_dist, inputs.light_irr = (N.ptr(ldist), N.ptr(lirr)) if len(ldist) else (None, None)
     cap = 2 * n  # (a refractive hit's two children; a Diffuse fan-out asks for more, below)
     for _ in range(2):
         arrs = {"origin": np.empty((3, cap)), "dir": np.empty((3, cap)), "weight": np.empty((3, cap)),
@@ -179,12 +283,18 @@ def shade_level(scene, material, ray, hit):
         kids.cap = cap
         for k, v in arrs.items():
             setattr(kids, k, N.ptr(v))
-        rc = lib.srt_shade_level(ctx, ctypes.byref(a), N.ptr(ids), N.ptr(t), N.ptr(o), ctypes.byref(kids), None)
+        if inputs is None:
+            rc = lib.srt_shade_level(ctx, ctypes.byref(a), N.ptr(ids), N.ptr(t), N.ptr(o), ctypes.byref(kids), None)
+        else:
+            rc = lib.srt_shade_level_inputs(ctx, ctypes.byref(a), N.ptr(ids), N.ptr(t), N.ptr(o),
+                                            ctypes.byref(inputs), ctypes.byref(kids), None)
         if rc != 0 and kids.n > cap:
             cap = int(kids.n)  # room for them all, then once more
             continue
         N.check(lib, rc)
         break
+    else:  # (the count the first attempt reported did not hold them: never read truncated children)
+        raise RuntimeError("srt_shade_level: %d children exceed the room made for them twice" % int(kids.n))
     color = [local[0].copy(), local[1].copy(), local[2].copy()]
     nk = int(kids.n)
     if nk:

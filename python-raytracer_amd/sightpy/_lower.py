@@ -337,7 +337,7 @@ def camera_desc(cam):
 
 
 def lower_scene(scene, extra_media=()):
-    from ._hybrid import is_hybrid, device_collider, device_material
+    from ._hybrid import is_hybrid, device_collider, device_material, device_light, user_texture
 
     L = Lowered()
     pool = _TexturePool()
@@ -391,9 +391,16 @@ def lower_scene(scene, extra_media=()):
             continue
         if getattr(m, "normalmap_u8", None) is not None:
             r["normalmap"] = pool.add(m.normalmap_u8, _RAW_LUT, repeat=m.repeat)
+        # a user texture subclass: its get_color(hit) runs on the host, the colour arrives per hit
+        # (srt_shade_level_inputs; _hybrid.shade_level)
+        hit_albedo = user_texture(m) is not None
+        if hit_albedo:
+            r["flags"] |= N.MF_HIT_ALBEDO
         if isinstance(m, Glossy):
             r["type"] = N.GLOSSY
-            if isinstance(m.diff_texture, image):
+            if hit_albedo:
+                pass
+            elif isinstance(m.diff_texture, image):
                 r["tex"] = pool.add(m.diff_texture.u8, _LIN_LUT, repeat=m.diff_texture.repeat)
             else:
                 p[0:3] = _f3(m.diff_texture.color * m.diff_coeff)
@@ -425,7 +432,9 @@ def lower_scene(scene, extra_media=()):
                 r["flags"] |= N.MF_NOISE
         elif isinstance(m, Diffuse):
             r["type"] = N.DIFFUSE
-            if isinstance(m.diff_texture, image):
+            if hit_albedo:
+                pass
+            elif isinstance(m.diff_texture, image):
                 r["tex"] = pool.add(m.diff_texture.u8, _LIN_LUT, repeat=m.diff_texture.repeat)
             else:
                 p[0:3] = _f3(m.diff_texture.color)
@@ -435,7 +444,9 @@ def lower_scene(scene, extra_media=()):
             L.has_diffuse = 1
         elif isinstance(m, Emissive):
             r["type"] = N.EMISSIVE
-            if isinstance(m.texture_color, image):
+            if hit_albedo:
+                pass
+            elif isinstance(m.texture_color, image):
                 r["tex"] = pool.add(m.texture_color.u8, _LIN_LUT, repeat=m.texture_color.repeat)
             else:
                 p[0:3] = _f3(m.texture_color.color)
@@ -477,7 +488,7 @@ def lower_scene(scene, extra_media=()):
         m = prim.material
         if isinstance(c, Triangle_Collider) and (
             getattr(m, "normalmap_u8", None) is not None
-            or isinstance(getattr(m, "diff_texture", None), image)
+            or (isinstance(getattr(m, "diff_texture", None), image) and user_texture(m) is None)
             or isinstance(m, ThinFilmInterference)
         ):
             raise NotImplementedError("Triangle uv is undefined in the reference (triangle.py:79-83)")
@@ -491,19 +502,31 @@ def lower_scene(scene, extra_media=()):
     lrecs = np.zeros(len(scene.Light_list), dtype=N.LIGHT_DTYPE)
     light_local = np.zeros((len(scene.Light_list), len(colliders), 3))
     for i, lt in enumerate(scene.Light_list):
-        if isinstance(lt, DirectionalLight):
+        if isinstance(lt, DirectionalLight) and device_light(lt):
             lrecs[i]["type"] = N.LIGHT_DIRECTIONAL
             lrecs[i]["dir"] = _f3(lt.Ldir)
             for j, c in enumerate(colliders):
                 if isinstance(c, Cuboid_Collider):
                     # shadow rays: D is a scalar vec3, so D.matmul goes through BLAS gemv
                     light_local[i, j] = _f3(lt.Ldir.matmul(c.basis_matrix))
-        elif isinstance(lt, PointLight):
+            lrecs[i]["color"] = _f3(lt.color)
+        elif isinstance(lt, PointLight) and device_light(lt):
             lrecs[i]["type"] = N.LIGHT_POINT
             lrecs[i]["pos"] = _f3(lt.pos)
+            lrecs[i]["color"] = _f3(lt.color)
         else:
-            raise NotImplementedError("light type %s" % type(lt).__name__)
-        lrecs[i]["color"] = _f3(lt.color)
+            # a user Light subclass: one direction for every hit; its get_distance / get_irradiance
+            # run on the host and arrive per hit (srt_shade_level_inputs)
+            Ld = lt.get_L()
+            if not (all(hasattr(Ld, k) for k in "xyz") and all(np.ndim(v) == 0 for v in (Ld.x, Ld.y, Ld.z))):
+                raise NotImplementedError(
+                    "light %s: get_L() is not a vec3 of three scalars; a per-ray light direction is not supported"
+                    % type(lt).__name__)
+            lrecs[i]["type"] = N.LIGHT_USER
+            lrecs[i]["dir"] = _f3(Ld)
+            for j, c in enumerate(colliders):
+                if isinstance(c, Cuboid_Collider):
+                    light_local[i, j] = _f3(Ld.matmul(c.basis_matrix))
     L.lights = lrecs
     L.light_local = np.ascontiguousarray(light_local)
 

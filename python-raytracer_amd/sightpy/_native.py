@@ -24,8 +24,8 @@ SRT_MATERIAL_PARAMS = 16
 SPHERE, PLANE, CUBOID, TRIANGLE = 0, 1, 2, 3
 GLOSSY, REFRACTIVE, THINFILM, DIFFUSE, EMISSIVE, SKY = 0, 1, 2, 3, 4, 5
 CF_SHADOW, CF_MC, CF_UV_CROSS = 1, 2, 4
-MF_ROUGH, MF_LIGHTMAP, MF_NOISE = 1, 2, 4
-LIGHT_DIRECTIONAL, LIGHT_POINT = 0, 1
+MF_ROUGH, MF_LIGHTMAP, MF_NOISE, MF_HIT_ALBEDO = 1, 2, 4, 8
+LIGHT_DIRECTIONAL, LIGHT_POINT, LIGHT_USER = 0, 1, 2
 
 ERR_ARG, ERR_HIP, ERR_NOSCENE, ERR_MEMORY, ERR_INDEX, ERR_DEPTH, ERR_NAME = -1, -2, -3, -4, -5, -6, -7
 
@@ -223,9 +223,19 @@ class Children(ctypes.Structure):
     ]
 
 
+class HitInputs(ctypes.Structure):
+    """srt_hit_inputs: what the user's texture / Light methods returned at each hit (srt_shade_level_inputs)."""
+    _fields_ = [
+        ("albedo", _p),
+        ("n_lights", ctypes.c_int32),
+        ("light_dist", _p),
+        ("light_irr", _p),
+    ]
+
+
 # name -> (restype, argtypes) for every entry point of include/sightpy_rt.h
 RENDER_ASYNC, RENDER_SHARDED, RENDER_GATHER_RGB, RENDER_RGB_ROWS, RENDER_RGB_LOCAL, RENDER_RGBX = 1, 2, 4, 8, 16, 32  # SRT_RENDER_*
-ABI_VERSION = 5  # SRT_ABI_VERSION of include/sightpy_rt.h
+ABI_VERSION = 6  # SRT_ABI_VERSION of include/sightpy_rt.h
 COMM_ID_BYTES = 128
 
 SIGNATURES = {
@@ -242,6 +252,8 @@ SIGNATURES = {
     "srt_shade": (ctypes.c_int, [_p, ctypes.POINTER(TraceArgs), _p, _p, _p, ctypes.POINTER(Stats)]),
     "srt_shade_level": (ctypes.c_int, [_p, ctypes.POINTER(TraceArgs), _p, _p, _p, ctypes.POINTER(Children),
                                        ctypes.POINTER(Stats)]),
+    "srt_shade_level_inputs": (ctypes.c_int, [_p, ctypes.POINTER(TraceArgs), _p, _p, _p, ctypes.POINTER(HitInputs),
+                                              ctypes.POINTER(Children), ctypes.POINTER(Stats)]),
     "srt_collider_surface": (ctypes.c_int, [_p, _p, _p, ctypes.c_int64, _p, _p, ctypes.c_int]),
     "srt_texture_lookup": (ctypes.c_int, [_p, _p, _p, ctypes.c_int64, _p, ctypes.c_int64, _p]),
     "srt_primary_rays": (ctypes.c_int, [_p, ctypes.POINTER(CameraDesc), _p, _p, _p]),

@@ -74,6 +74,11 @@ class Scene:
         gathered over RCCL (the reference's
         multiprocessing.Pool over samples, scene.py:80-116, is replaced); the image does not depend
         on the number of GPUs.
+
+        A scene holding user subclasses of Collider, Material, texture or Light is rendered by the
+        host-driven recursion of `_hybrid.py` (their methods on the host, every built-in step on the
+        device; a user texture's colour and a user light's distance and irradiance reach the device
+        shaders per hit).
         """
         from . import _backend as B
         from . import _hybrid
@@ -84,8 +89,9 @@ class Scene:
             raise ValueError("rng must be 'numpy', 'numpy-host' or 'device'")
         H, W = int(self.camera.screen_height), int(self.camera.screen_width)
         if _hybrid.is_hybrid(self):
-            # user Collider / Material subclasses: the reference's recursion driven from the host,
-            # the built-in steps on the device (_hybrid.py); numpy's stream as the reference draws it
+            # user Collider / Material / texture / Light subclasses: the reference's recursion driven
+            # from the host, the built-in steps on the device (_hybrid.py); numpy's stream as the
+            # reference draws it
             from .utils.colour_functions import sRGB_linear_to_sRGB
 
             lin = _hybrid.render_linear(self, samples_per_pixel)
