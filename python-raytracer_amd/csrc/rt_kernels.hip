@@ -1794,59 +1794,61 @@ void free_list(std::vector<void*>& v) {
     v.clear();
 }
 
-// make room for `rays` queued rays per depth (spread over the shards with slack)
-int ensure_queues(srt_ctx* c, int64_t rays) {
-    int64_t seg = (rays + NSHARD - 1) / NSHARD;
-    seg = seg + seg / 8 + 1024;
-    if (seg <= c->f->seg) return SRT_OK;
-    free_list(c->f->queue_bufs);
-    c->f->seg = 0;
-    const int64_t n = seg * NSHARD;
-    for (int k = 0; k < 2; ++k) {
-        Queue& q = c->f->q[k];
-        double** dptr[9] = {&q.ox, &q.oy, &q.oz, &q.dx, &q.dy, &q.dz, &q.wr, &q.wg, &q.wb};
-        for (double** p : dptr) {
-            if (dalloc(p, n) != hipSuccess) return fail(SRT_ERR_MEMORY, "ray queue allocation failed");
-            c->f->queue_bufs.push_back(*p);
-        }
-        uint32_t** uptr[3] = {&q.pix, &q.meta, &q.path};
-        for (uint32_t** p : uptr) {
-            if (dalloc(p, n) != hipSuccess) return fail(SRT_ERR_MEMORY, "ray queue allocation failed");
-            c->f->queue_bufs.push_back(*p);
-        }
+// the twelve arrays of a ray queue, `n` rays each (recorded in `bufs`)
+int alloc_queue(Queue& q, int64_t n, std::vector<void*>& bufs, const char* what) {
+    double** dptr[9] = {&q.ox, &q.oy, &q.oz, &q.dx, &q.dy, &q.dz, &q.wr, &q.wg, &q.wb};
+    for (double** p : dptr) {
+        if (dalloc(p, n) != hipSuccess) return fail(SRT_ERR_MEMORY, what);
+        bufs.push_back(*p);
     }
-    c->f->seg = seg;
+    uint32_t** uptr[3] = {&q.pix, &q.meta, &q.path};
+    for (uint32_t** p : uptr) {
+        if (dalloc(p, n) != hipSuccess) return fail(SRT_ERR_MEMORY, what);
+        bufs.push_back(*p);
+    }
+    return SRT_OK;
+}
+
+// segment length of queues for `rays` queued rays per depth (spread over the shards with slack)
+int64_t queue_seg_for(int64_t rays) {
+    const int64_t seg = (rays + NSHARD - 1) / NSHARD;
+    return seg + seg / 8 + 1024;
+}
+
+// make room for `rays` queued rays per depth
+int ensure_queues(FrameSlot& f, int64_t rays) {
+    const int64_t seg = queue_seg_for(rays);
+    if (seg <= f.seg) return SRT_OK;
+    free_list(f.queue_bufs);
+    f.seg = 0;
+    for (Queue& q : f.q)
+        if (int rc = alloc_queue(q, seg * NSHARD, f.queue_bufs, "ray queue allocation failed")) return rc;
+    f.seg = seg;
     return SRT_OK;
 }
 
 // rings of the frame kernel: more rings than waves can ever be resident (32 per CU), so a wave
 // always finds a free one; `cap` rays each (power of two)
-int ensure_ring(srt_ctx* c, int64_t cap) {
+int64_t ring_cap_for(int64_t cap) {
     int64_t k = 256;
     while (k < cap) k <<= 1;
-    cap = k;
-    const int nslot = std::max(1024, 2 * 32 * c->ncu);
-    if (cap <= c->f->ring_cap && nslot <= c->f->nslot) return SRT_OK;
-    free_list(c->f->ring_bufs);
-    c->f->ring_cap = 0;
-    c->f->nslot = 0;
-    const int64_t n = cap * nslot;
-    Queue& q = c->f->ring;
-    double** dptr[9] = {&q.ox, &q.oy, &q.oz, &q.dx, &q.dy, &q.dz, &q.wr, &q.wg, &q.wb};
-    for (double** p : dptr) {
-        if (dalloc(p, n) != hipSuccess) return fail(SRT_ERR_MEMORY, "ray ring allocation failed");
-        c->f->ring_bufs.push_back(*p);
-    }
-    uint32_t** uptr[3] = {&q.pix, &q.meta, &q.path};
-    for (uint32_t** p : uptr) {
-        if (dalloc(p, n) != hipSuccess) return fail(SRT_ERR_MEMORY, "ray ring allocation failed");
-        c->f->ring_bufs.push_back(*p);
-    }
-    if (dalloc(&c->f->ring_lock, nslot) != hipSuccess) return fail(SRT_ERR_MEMORY, "ring lock allocation failed");
-    c->f->ring_bufs.push_back(c->f->ring_lock);
-    HIP_TRY(hipMemset(c->f->ring_lock, 0, (size_t)nslot * 4));
-    c->f->ring_cap = cap;
-    c->f->nslot = nslot;
+    return k;
+}
+int ring_slots(const srt_ctx* c) { return std::max(1024, 2 * 32 * c->ncu); }
+
+int ensure_ring(srt_ctx* c, FrameSlot& f, int64_t cap) {
+    cap = ring_cap_for(cap);
+    const int nslot = ring_slots(c);
+    if (cap <= f.ring_cap && nslot <= f.nslot) return SRT_OK;
+    free_list(f.ring_bufs);
+    f.ring_cap = 0;
+    f.nslot = 0;
+    if (int rc = alloc_queue(f.ring, cap * nslot, f.ring_bufs, "ray ring allocation failed")) return rc;
+    if (dalloc(&f.ring_lock, nslot) != hipSuccess) return fail(SRT_ERR_MEMORY, "ring lock allocation failed");
+    f.ring_bufs.push_back(f.ring_lock);
+    HIP_TRY(hipMemset(f.ring_lock, 0, (size_t)nslot * 4));
+    f.ring_cap = cap;
+    f.nslot = nslot;
     return SRT_OK;
 }
 
@@ -1942,12 +1944,12 @@ int check_flags(uint32_t f0) {
     return SRT_OK;
 }
 
-TraceParams base_params(srt_ctx* c, uint64_t seed) {
+TraceParams base_params(const srt_ctx* c, const FrameSlot& f, uint64_t seed) {
     TraceParams P{};
     P.S = c->S;
-    P.flags = c->f->flags;
-    P.shadow = c->f->shadow;
-    P.seg = c->f->seg;
+    P.flags = f.flags;
+    P.shadow = f.shadow;
+    P.seg = f.seg;
     P.seed = seed;
     P.lane_stats = c->lane_stats;  // (read by k_primary_lean<.., true> only)
     return P;
@@ -1986,33 +1988,22 @@ size_t lut_bytes(const srt_ctx* c) { return (size_t)c->S.nlut_lds * 256 * sizeof
 
 int trace_grid(const srt_ctx* c) { return std::max(NSHARD, (c->max_blocks / NSHARD) * NSHARD); }
 
-// copy `bytes` from host `src` to device `dst` unless `shadow` (the host copy of what dst holds)
-// already equals it.  The shadow is invalidated whenever the buffer is reallocated (ensure_buf).
-int finish_async(srt_ctx* c, srt_stats* st);
+int wait_frames(srt_ctx* c, srt_stats* st);
 
-// the camera tables are shared by the frame slots: wait for the frames in flight before changing
-// them (keeps the current slot)
-int quiesce_for_shared_write(srt_ctx* c) {
-    if (c->async_pending == 0) return SRT_OK;
-    FrameSlot* keep = c->f;
-    int rc = finish_async(c, nullptr);
-    c->f = keep;
-    return rc;
-}
-
-int upload_if_changed(srt_ctx* c, void* dst, std::vector<uint8_t>& shadow, const void* src, size_t bytes) {
-    if (is_device_ptr(src)) {
-        int rc = quiesce_for_shared_write(c);
-        if (rc) return rc;
-        shadow.clear();
-        HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->f->stream));
-        return SRT_OK;
-    }
-    if (shadow.size() == bytes && !memcmp(shadow.data(), src, bytes)) return SRT_OK;
-    int rc = quiesce_for_shared_write(c);
+// copy `bytes` from host `src` to device `dst` (on `st`) unless `shadow` (the host copy of what dst
+// holds) already equals it.  The shadow is invalidated whenever the buffer is reallocated (ensure_buf).
+// The camera tables are shared by the frame slots: the frames in flight are waited for before a change.
+int upload_if_changed(srt_ctx* c, hipStream_t st, void* dst, std::vector<uint8_t>& shadow, const void* src,
+                      size_t bytes) {
+    const bool dev = is_device_ptr(src);
+    if (!dev && shadow.size() == bytes && !memcmp(shadow.data(), src, bytes)) return SRT_OK;
+    int rc = c->async_pending > 0 ? wait_frames(c, nullptr) : SRT_OK;
     if (rc) return rc;
-    shadow.assign((const uint8_t*)src, (const uint8_t*)src + bytes);
-    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->f->stream));
+    if (dev)
+        shadow.clear();
+    else
+        shadow.assign((const uint8_t*)src, (const uint8_t*)src + bytes);
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
     return SRT_OK;
 }
 
@@ -2329,15 +2320,15 @@ int mt_launch(srt_ctx* c, hipStream_t st, uint32_t* win, const uint32_t* key, in
 // and kernel times of the frame's passes.  Returns SRT_RETRY_OVERFLOW when a queue shard overflowed.
 // `retry` receives the RETRY_* bits of every pass.
 constexpr int SRT_RETRY = 1;
-int collect_frame(srt_ctx* c, const FramePlan& F, srt_stats& S, uint32_t* retry = nullptr) {
+int collect_frame(srt_ctx* c, const FrameSlot& f, const FramePlan& F, srt_stats& S, uint32_t* retry = nullptr) {
     uint32_t bits = 0;
     for (int p = 0; p < F.npass; ++p) {
-        const uint32_t* hp = c->f->host + p * F.pass_words;
+        const uint32_t* hp = f.host + p * F.pass_words;
         int rc;
         if ((rc = check_flags(hp[F.cnt_words]))) return rc;
         bits |= hp[F.cnt_words + 1];
     }
-    bits |= c->f->host[F.npass * F.pass_words + 2];
+    bits |= f.host[F.npass * F.pass_words + 2];
     if (bits & RETRY_CHAIN_TIE) c->chain_ok = false;  // no chain mode for this scene any more
     if (bits & RETRY_FIXED_RANGE) c->fx_ok = false;   // f64 atomics for this scene
     if (retry) *retry = bits;
@@ -2345,8 +2336,8 @@ int collect_frame(srt_ctx* c, const FramePlan& F, srt_stats& S, uint32_t* retry 
     double ms_trace = 0.0, ms_primary = 0.0;
     for (int d = 0; d < SRT_MAX_DEPTHS; ++d) S.rays_per_depth[d] = 0;
     for (int p = 0; p < F.npass; ++p) {
-        const uint32_t* hp = c->f->host + p * F.pass_words;
-        if (depth_total(hp + (int64_t)(F.dcap + 1) * NSHARD, (F.frame || F.fuse) ? INT64_MAX : c->f->seg) != 0)
+        const uint32_t* hp = f.host + p * F.pass_words;
+        if (depth_total(hp + (int64_t)(F.dcap + 1) * NSHARD, (F.frame || F.fuse) ? INT64_MAX : f.seg) != 0)
             return fail(SRT_ERR_DEPTH, "rays alive after the depth cap");
         if (F.frame) {
             // k_frame counts every ray it traces (per shard), depth 0 included
@@ -2355,16 +2346,16 @@ int collect_frame(srt_ctx* c, const FramePlan& F, srt_stats& S, uint32_t* retry 
         } else {
             S.rays_per_depth[0] += (int64_t)std::min(F.batch, F.spp - p * F.batch) * F.npix;
             for (int d = 1; d <= F.dcap; ++d)
-                S.rays_per_depth[d] += depth_total(hp + (int64_t)d * NSHARD, F.fuse ? INT64_MAX : c->f->seg);
+                S.rays_per_depth[d] += depth_total(hp + (int64_t)d * NSHARD, F.fuse ? INT64_MAX : f.seg);
         }
-        const hipEvent_t* ev = c->f->ev.data() + (int64_t)p * F.nev;
+        const hipEvent_t* ev = f.ev.data() + (int64_t)p * F.nev;
         float ms;
         HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
         ms_primary += ms;
         HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[F.chain_from > 0 ? F.chain_from + 1 : F.dcap + 1]));
         ms_trace += ms;
     }
-    const uint32_t* hshadow = c->f->host + F.npass * F.pass_words;
+    const uint32_t* hshadow = f.host + F.npass * F.pass_words;
     S.passes = F.npass;
     S.ms_trace_kernels = ms_trace;
     S.ms_primary_kernel = ms_primary;
@@ -2382,12 +2373,12 @@ int collect_frame(srt_ctx* c, const FramePlan& F, srt_stats& S, uint32_t* retry 
 }
 
 // zero the pinned flag words of every pass (only while no frame is in flight)
-void clear_host_flags(srt_ctx* c, const FramePlan& F) {
+void clear_host_flags(FrameSlot& f, const FramePlan& F) {
     for (int p = 0; p < F.npass; ++p) {
-        c->f->host[p * F.pass_words + F.cnt_words] = 0u;
-        c->f->host[p * F.pass_words + F.cnt_words + 1] = 0u;
+        f.host[p * F.pass_words + F.cnt_words] = 0u;
+        f.host[p * F.pass_words + F.cnt_words + 1] = 0u;
     }
-    c->f->host[F.npass * F.pass_words + 2] = 0u;  // k_resolve's fixed-point range check
+    f.host[F.npass * F.pass_words + 2] = 0u;  // k_resolve's fixed-point range check
 }
 
 // Stream and counters of a slot, created on first use.
@@ -2424,11 +2415,10 @@ void free_slot(FrameSlot& f) {
 
 // Wait for the asynchronous frames in flight and check them (flags accumulated over all of them,
 // stats of the last).  An overflow grows the queues and is reported as an error: those frames are
-// wrong and must be rendered again.  Leaves slot 0 current.
-int finish_async(srt_ctx* c, srt_stats* st) {
+// wrong and must be rendered again.
+int wait_frames(srt_ctx* c, srt_stats* st) {
     c->retry_frame = false;
     if (c->async_pending == 0) {
-        c->f = &c->slots[0];
         if (st) *st = c->async_stats;
         return SRT_OK;
     }
@@ -2446,16 +2436,15 @@ int finish_async(srt_ctx* c, srt_stats* st) {
     for (int k = 0; k < MAX_FRAME_SLOTS; ++k) {
         FrameSlot& f = c->slots[(c->last_slot + 1 + k) % MAX_FRAME_SLOTS];  // the last frame's slot last
         if (!f.pending) continue;
-        c->f = &f;
         srt_stats S{};
         uint32_t bits = 0;
-        int rc = collect_frame(c, f.plan, S, &bits);
-        clear_host_flags(c, f.plan);
+        int rc = collect_frame(c, f, f.plan, S, &bits);
+        clear_host_flags(f, f.plan);
         f.pending = 0;
         if (rc == SRT_RETRY) {
             overflow = true;
             if ((bits & RETRY_OVERFLOW) &&
-                (rc = f.plan.frame ? ensure_ring(c, 2 * f.ring_cap) : ensure_queues(c, 2 * f.seg * NSHARD))) {
+                (rc = f.plan.frame ? ensure_ring(c, f, 2 * f.ring_cap) : ensure_queues(f, 2 * f.seg * NSHARD))) {
                 first_err = first_err ? first_err : rc;
             }
         } else if (rc) {
@@ -2464,7 +2453,6 @@ int finish_async(srt_ctx* c, srt_stats* st) {
             last = S;
         }
     }
-    c->f = &c->slots[0];
     if (first_err) return first_err;
     c->retry_frame = overflow;
     if (overflow)
@@ -2474,6 +2462,13 @@ int finish_async(srt_ctx* c, srt_stats* st) {
     c->async_stats = last;
     if (st) *st = last;
     return SRT_OK;
+}
+
+// wait_frames for the entry points: leaves slot 0 current
+int finish_async(srt_ctx* c, srt_stats* st) {
+    const int rc = wait_frames(c, st);
+    c->f = &c->slots[0];
+    return rc;
 }
 
 int64_t shard_npix(const FrameSlot::Gather& G, int nranks, int q) {
@@ -2889,702 +2884,7 @@ int srt_upload_scene(srt_ctx* c, const srt_scene_desc* d) {
 
 
 }  // extern "C"
-namespace {
-// srt_render, or with `prefetch` srt_render_prefetch: the same planning, then only the first pass's
-// numpy-stream generation is queued (srt_ctx::pf) and the call returns
-int render_impl(srt_ctx* c, const srt_camera* cam, const srt_render_args* a, srt_stats* st, bool prefetch) {
-    auto t_start = std::chrono::steady_clock::now();
-    if (!c || !cam || !a) return fail(SRT_ERR_ARG, "null argument");
-    const srt_ctx::MtPrefetch pf_in = c->pf;  // (a prefetch is used by the next render only)
-    c->pf.valid = false;
-    if (!prefetch && !c->has_scene) return fail(SRT_ERR_NOSCENE, "no scene uploaded");
-    if (c->has_scene && c->needs_inputs) return refuse_inputs_scene(prefetch ? "srt_render_prefetch" : "srt_render");
-    if (a->flags & ~(SRT_RENDER_ASYNC | SRT_RENDER_SHARDED | SRT_RENDER_GATHER_RGB | SRT_RENDER_RGB_ROWS |
-                     SRT_RENDER_RGB_LOCAL | SRT_RENDER_RGBX))
-        return fail(SRT_ERR_ARG, "unknown render flag");
-    if ((a->flags & SRT_RENDER_RGBX) && (a->flags & SRT_RENDER_SHARDED))
-        return fail(SRT_ERR_ARG, "SRT_RENDER_RGBX: not with SRT_RENDER_SHARDED");
-    if ((a->flags & SRT_RENDER_RGB_LOCAL) && (a->out_rgb || (a->flags & (SRT_RENDER_GATHER_RGB | SRT_RENDER_RGB_ROWS))))
-        return fail(SRT_ERR_ARG, "SRT_RENDER_RGB_LOCAL needs out_rgb NULL and no SRT_RENDER_GATHER_RGB / RGB_ROWS");
-    if ((a->flags & SRT_RENDER_RGB_ROWS) &&
-        (!(a->flags & SRT_RENDER_SHARDED) || (a->flags & SRT_RENDER_GATHER_RGB) || !a->out_rgb))
-        return fail(SRT_ERR_ARG, "SRT_RENDER_RGB_ROWS needs SRT_RENDER_SHARDED, out_rgb and no SRT_RENDER_GATHER_RGB");
-    const bool async = (a->flags & SRT_RENDER_ASYNC) != 0;
-    const bool sharded = (a->flags & SRT_RENDER_SHARDED) != 0;
-    if (a->spp <= 0 || cam->width <= 0 || cam->height <= 0 || (!sharded && a->n_rows <= 0) || !cam->xs || !cam->ys)
-        return fail(SRT_ERR_ARG, "spp, width, height, n_rows must be positive and xs/ys set");
-    if (a->jitter && a->mt) return fail(SRT_ERR_ARG, "jitter and mt are exclusive");
-    const bool use_mt = a->mt != nullptr;
-    if (use_mt && (a->mt->pos < 0 || a->mt->pos > rtmt::N)) return fail(SRT_ERR_ARG, "bad numpy RNG position");
-    // a prefetch covers synchronous whole frames drawing numpy's stream (Scene.render); others: nothing
-    if (prefetch && (async || sharded || !use_mt || a->rows || a->n_rows != cam->height)) return SRT_OK;
-    // rows of this call
-    std::vector<int32_t> rows_h;
-    const int32_t* rows_src = nullptr;
-    int n_rows = a->n_rows;
-    int64_t band = 1;  // row-band height of a sharded frame
-    if (sharded) {
-        if (c->nranks > MAX_RANKS) return fail(SRT_ERR_ARG, "too many ranks");
-        if (cam->height < c->nranks) return fail(SRT_ERR_ARG, "a sharded frame needs at least one row per rank");
-        if (a->out_hit_id) return fail(SRT_ERR_ARG, "hit ids of a sharded frame are not gathered");
-        band = shard_band_height(cam->height, c->nranks, shard_kmax(cam->height, c->nranks, c->shard_bands, c->fanout));
-        rows_h = band_rows(cam->height, c->nranks, c->rank, band);
-        n_rows = (int)rows_h.size();
-        if (n_rows == 0) return fail(SRT_ERR_ARG, "a sharded frame left this rank without rows");
-        rows_src = rows_h.data();
-    } else if (a->rows) {
-        if (is_device_ptr(a->rows)) return fail(SRT_ERR_ARG, "rows must be host memory");
-        for (int k = 0; k < a->n_rows; ++k)
-            if (a->rows[k] < 0 || a->rows[k] >= cam->height) return fail(SRT_ERR_ARG, "row index out of range");
-        rows_src = a->rows;
-    } else {
-        if (a->n_rows > cam->height) return fail(SRT_ERR_ARG, "n_rows > height");
-        rows_h.resize(a->n_rows);
-        for (int k = 0; k < a->n_rows; ++k) rows_h[k] = k;
-        rows_src = rows_h.data();
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    const int64_t W = cam->width, Hf = cam->height;
-    const int64_t npix = (int64_t)n_rows * W;
-    if (W * Hf >= ((int64_t)1 << 31)) return fail(SRT_ERR_ARG, "image too large");
-    const int jk = ptr_kind(a->jitter), hk = ptr_kind(a->out_hit_id);
-    const int rk = ptr_kind(a->out_rgb), uk = ptr_kind(a->out_srgb8);
-    const bool jit_dev = jk == 1, hit_dev = hk == 1, rgb_dev = rk == 1, u8_dev = uk == 1;
-    if (async && (jk >= 2 || hk >= 2 || rk == 3 || uk == 3))
-        return fail(SRT_ERR_ARG, "an asynchronous render takes device (or NULL) jitter and hit ids, and device or "
-                                 "pinned host (srt_host_alloc) outputs");
-    // outputs written by this rank: a shard's tiles stay on the device (the gather reads them); rank 0
-    // of a sharded frame writes the whole frame to the caller's buffers after the gather
-    const bool gather_rgb = sharded && (a->flags & SRT_RENDER_GATHER_RGB) != 0;
-    const bool rgb_rows = sharded && (a->flags & SRT_RENDER_RGB_ROWS) != 0;
-    if (rgb_rows && ptr_kind(a->out_rgb) != 2)
-        return fail(SRT_ERR_ARG, "SRT_RENDER_RGB_ROWS: out_rgb must be pinned or registered host memory");
-    int rc;
-    // samples per pass: both queues must hold spp_pass * npix * fanout rays
-    const int64_t per_sample = npix * c->fanout;
-    const int64_t budget_rays = c->queue_budget / (2 * RAY_BYTES);
-    int batch = a->batch_spp > 0 ? a->batch_spp
-                                 : (int)std::max<int64_t>(1, std::min<int64_t>(1 << 20, budget_rays / per_sample));
-    batch = std::min(batch, a->spp);
-    while (batch > 1 && (int64_t)batch * npix * c->fanout >= ((int64_t)1 << 32) - 1) batch /= 2;
-    // the numpy stream of a pass (its samples of the whole frame) is generated into the jitter buffer
-    if (use_mt) while (batch > 1 && (int64_t)batch * 4 * W * Hf * 8 > ((int64_t)8 << 30)) batch /= 2;
-    FramePlan F;
-    F.npix = npix;
-    F.W = W;
-    F.H = Hf;
-    F.sharded = sharded;
-    F.gather_rgb = gather_rgb;
-    F.use_mt = use_mt;
-    F.spp = a->spp;
-    F.batch = batch;
-    F.npass = (a->spp + batch - 1) / batch;
-    F.dcap = depth_cap(c);
-    F.nev = F.dcap + 2;  // events per pass: before k_primary, after each depth
-    F.cnt_words = (int64_t)SRT_MAX_DEPTHS * NSHARD;
-    F.pass_words = F.cnt_words + 2;
-    F.frame = c->use_frame < 0 ? c->fanout > 1 : c->use_frame != 0;
-    const int64_t ntiles = frame_tiles(frame_tile_for(pick_variant(c->mats, c->seq_on ? c->seq : 0).mats), W, npix / W);
-    if (F.frame) {
-        // a frame kernel block traces one 64-pixel tile through the pass's samples: a small frame (a
-        // shard of a multi-GPU frame) has too few tiles to fill the GPU, so its samples are split
-        // into groups, one block per (tile, group), until there are ~4 blocks per resident wave
-        // slot (c->max_blocks = 4 OCC per CU)
-        const int64_t want = 4 * (int64_t)c->max_blocks;
-        const int64_t g = (want + ntiles - 1) / ntiles;
-        F.groups = (int)std::max<int64_t>(1, std::min<int64_t>(g, batch));
-    }
-    // fused paths (single-child scenes): by default when the frame's threads (sample groups
-    // included, pix_groups) fill two rounds of the resident threads
-    F.fuse = !F.frame && c->fanout == 1 && c->chain_ok && pick_variant(c->mats, c->seq_on ? c->seq : 0).fused &&
-             (c->fuse_primary > 0 ||
-              (c->fuse_primary < 0 && npix * pix_groups(c, npix, batch, true) >= fused_items(c)));
-    if (!F.fuse && !F.frame && c->fanout == 1 && c->chain_ok && c->hint_key[0] == npix && c->hint_key[1] == a->spp &&
-        c->hint_key[2] == batch) {
-        for (int d = 1; d <= F.dcap; ++d)
-            if (c->hint[d] < c->chain_rays) { F.chain_from = d; break; }
-    }
-    // the slot of this frame: slot 0 for a synchronous frame (after the frames in flight),
-    // alternating slots for asynchronous ones
-    if (!async) {
-        if ((rc = finish_async(c, nullptr))) return rc;
-    } else {
-        FrameSlot& f = c->slots[c->next_slot];
-        if ((rc = ensure_slot(f))) return rc;
-        c->f = &f;
-    }
-    // numpy stream of a shard (rows not the whole frame): band mode, only the rows' runs generated
-    // (rt_mt_kernel.h MtArgs::bands); tables for the full passes and the last pass
-    const int mt_pm = cam->lens_radius != 0.0 ? 15 : 3;  // a pinhole camera reads planes 0 and 1 only
-    const srt_ctx::MtBandTab* mt_bt[2] = {nullptr, nullptr};
-    int64_t mt_win_need = (int64_t)rtmt::SEGS * rtmt::N;
-    // (the band tables and end polynomials are kept per frame shape; a context that has seen many
-    // shapes drops them between frames, when no frame in flight reads them)
-    if (c->async_pending == 0 && (c->mt_bandtabs.size() >= 16 || c->mt_end_polys.size() >= 64)) {
-        HIP_TRY(hipDeviceSynchronize());
-        for (auto& t : c->mt_bandtabs) {
-            (void)hipFree(t.bands);
-            (void)hipFree(t.polys);
-        }
-        c->mt_bandtabs.clear();
-        for (auto& e : c->mt_end_polys) (void)hipFree(e.second);
-        c->mt_end_polys.clear();
-    }
-    // a whole frame with nothing in flight (synchronous, or the first of a pipeline): short segments in
-    // band mode (srt_ctx::mt_short); later pipelined frames generate behind their predecessors in
-    // band-mode segments of mt_pipe_split doubles (0: the tabulated 2^19-word segments)
-    const int64_t whole_split = n_rows < Hf ? 0
-                              : c->async_pending == 0 ? c->mt_short
-                                                                           : c->mt_pipe_split;
-    if (use_mt && c->mt_bands_on && (n_rows < Hf || whole_split > 0)) {
-        const int last_ns = a->spp - (F.npass - 1) * batch;
-        const int64_t split = n_rows < Hf ? (int64_t)1 << 18 : whole_split;
-        for (int k = 0; k < 2; ++k) {
-            if ((rc = mt_band_table(c, W, Hf, k == 0 ? batch : last_ns, mt_pm, rows_src, n_rows, split, &mt_bt[k])))
-                return rc;
-            if (mt_bt[k]) mt_win_need = std::max(mt_win_need, (int64_t)(mt_bt[k]->nseg + 1) * rtmt::N);
-        }
-        if (!mt_bt[0] || !mt_bt[1]) mt_bt[0] = mt_bt[1] = nullptr;
-    }
-    // band mode stores a shard's jitter in its own layout [s][plane][its rows][W] (1/N of the frame's)
-    // when every pass generates in band mode (a pass whose generation ends inside the key window
-    // takes the tabulated segments and the frame's layout)
-    auto pass_words = [&](int ns, bool last) { return 2 * ((int64_t)ns * 4 * W * Hf + (last ? 4 * W * Hf : 0)); };
-    const bool jit_compact = mt_bt[0] && rtmt::end_jump(pass_words(a->spp - (F.npass - 1) * batch, true)) > 0 &&
-                             (F.npass == 1 || rtmt::end_jump(pass_words(batch, false)) > 0);
-    const int64_t jit_doubles = use_mt ? (int64_t)batch * 4 * (jit_compact ? npix : W * Hf)
-                                       : (a->jitter && !jit_dev ? (int64_t)batch * 4 * npix : 0);
-    const int64_t maxpix = sharded ? shard_max_rows(Hf, c->nranks, band) * W : 0;  // the gather's tile
-    // rank 0's assembly rehearsed (srt_ctx::rehearse_assemble): these rows are rank 0's of an n-rank job
-    int reh_n = 0;
-    int64_t reh_band = 1, reh_maxpix = 0;
-    if (c->rehearse_assemble > 1 && !sharded && a->rows && a->out_srgb8 && ptr_kind(a->out_srgb8) != 1 &&
-        !(a->flags & SRT_RENDER_RGBX)) {
-        const int n = c->rehearse_assemble;
-        reh_band = shard_band_height(Hf, n, shard_kmax(Hf, n, c->shard_bands, c->fanout));
-        const std::vector<int32_t> r0 = band_rows(Hf, n, 0, reh_band);
-        if ((int)r0.size() == n_rows && std::equal(r0.begin(), r0.end(), rows_src)) {
-            reh_n = n;
-            reh_maxpix = shard_max_rows(Hf, n, reh_band) * W;
-        }
-    }
-    // frames in flight use the buffers below: a frame that would reallocate anything first waits
-    // for them (and reports their errors)
-    if (async && c->async_pending > 0) {
-        const FramePlan& pp = c->f->pending ? c->f->plan : c->slots[c->last_slot].plan;
-        const bool same = W <= c->cam_cap[0] && cam->height <= c->cam_cap[1] && n_rows <= c->cam_cap[2] &&
-                          3 * npix <= c->f->fb_cap && fx_words(npix) <= c->f->fbx_cap && 3 * npix <= c->f->rgb_cap &&
-                          3 * npix <= c->f->u8_cap &&
-                          jit_doubles <= c->f->jit_cap && (!use_mt || (mt_win_need <= c->f->mt_win_cap && !c->mt_dirty)) &&
-                          (F.frame || (int64_t)batch * npix * c->fanout <= c->f->seg * NSHARD) &&
-                          (!F.frame || c->f->ring_cap > 0) && F.npass == pp.npass && F.dcap == pp.dcap &&
-                          F.frame == pp.frame && F.chain_from == pp.chain_from && F.fuse == pp.fuse && F.W == pp.W && F.H == pp.H &&
-                          F.groups == pp.groups && (F.groups == 1 || (int64_t)F.groups * 3 * npix <= c->f->fbg_cap) &&
-                          F.sharded == pp.sharded && F.gather_rgb == pp.gather_rgb && F.use_mt == pp.use_mt &&
-                          (!reh_n || (c->f->g_u8_cap >= reh_n * reh_maxpix * 3 && c->f->full_u8_cap >= 3 * W * Hf)) &&
-                          (!(a->flags & SRT_RENDER_RGBX) || c->f->full_u8_cap >= 4 * npix) &&
-                          (!sharded || c->rank != 0 ||
-                           (c->f->g_u8_cap >= c->nranks * maxpix * 3 && c->f->full_u8_cap >= 3 * W * Hf &&
-                            (!gather_rgb || (c->f->g_rgb_cap >= c->nranks * maxpix * 3 && c->f->full_rgb_cap >= 3 * W * Hf)))) &&
-                          (int)c->f->ev.size() >= F.npass * F.nev && c->f->host_words >= F.npass * F.pass_words + 2;
-        if (!same) {
-            FrameSlot* keep = c->f;
-            if ((rc = finish_async(c, nullptr))) return rc;
-            c->f = keep;
-        }
-    }
-    {
-        const void* old[3] = {c->xs, c->ys, c->rows};
-        if ((rc = ensure_buf(&c->xs, c->cam_cap[0], W))) return rc;
-        if ((rc = ensure_buf(&c->ys, c->cam_cap[1], cam->height))) return rc;
-        if ((rc = ensure_buf(&c->rows, c->cam_cap[2], n_rows))) return rc;
-        const void* now[3] = {c->xs, c->ys, c->rows};
-        for (int k = 0; k < 3; ++k)
-            if (old[k] != now[k]) c->cam_host[k].clear();
-    }
-    // camera tables: uploaded only when they change (a render loop re-sends the same ones)
-    if ((rc = upload_if_changed(c, c->xs, c->cam_host[0], cam->xs, (size_t)W * 8))) return rc;
-    if ((rc = upload_if_changed(c, c->ys, c->cam_host[1], cam->ys, (size_t)cam->height * 8))) return rc;
-    if ((rc = upload_if_changed(c, c->rows, c->cam_host[2], rows_src, (size_t)n_rows * 4))) return rc;
-    if (use_mt && (rc = mt_ensure(c))) return rc;
-    // per-slot buffers of this frame shape (for an asynchronous frame also those of the other slot
-    // while it is idle, so that the pipeline's first frame on it allocates nothing)
-    auto ensure_frame = [&](FrameSlot& fs) -> int {
-        FrameSlot* keep = c->f;
-        c->f = &fs;
-        int r = SRT_OK;
-        if (!r) r = ensure_buf(&c->f->fb, c->f->fb_cap, 3 * npix);
-        if (!r && F.groups > 1) r = ensure_buf(&c->f->fbg, c->f->fbg_cap, (int64_t)F.groups * 3 * npix);
-        if (!r) r = ensure_buf(&c->f->fbx, c->f->fbx_cap, fx_words(npix));
-        if (!r) r = ensure_buf(&c->f->rgb, c->f->rgb_cap, 3 * npix);
-        if (!r) r = ensure_buf(&c->f->u8, c->f->u8_cap, 3 * npix);
-        if (!r && jit_doubles > 0) r = ensure_buf(&c->f->jit, c->f->jit_cap, jit_doubles);
-        if (!r && use_mt) r = mt_win_ensure(c, *c->f, mt_win_need);
-        if (!r && a->out_hit_id && !hit_dev) r = ensure_buf(&c->f->hit, c->f->hit_cap, (int64_t)batch * npix);
-        if (!r && (a->flags & SRT_RENDER_RGBX)) r = ensure_buf(&c->f->full_u8, c->f->full_u8_cap, 4 * npix);
-        if (!r && reh_n) {
-            const int64_t had = c->f->g_u8_cap;
-            r = ensure_buf(&c->f->g_u8, c->f->g_u8_cap, reh_n * reh_maxpix * 3);
-            if (!r && c->f->g_u8_cap != had && hipMemset(c->f->g_u8, 0, (size_t)c->f->g_u8_cap) != hipSuccess)
-                r = fail(SRT_ERR_HIP, "hipMemset failed");  // (stand-in tiles: defined bytes)
-            if (!r) r = ensure_buf(&c->f->full_u8, c->f->full_u8_cap, 3 * W * Hf);
-        }
-        if (!r && sharded && c->rank == 0) {
-            r = ensure_buf(&c->f->g_u8, c->f->g_u8_cap, c->nranks * maxpix * 3);
-            if (!r) r = ensure_buf(&c->f->full_u8, c->f->full_u8_cap, 3 * W * Hf);
-            if (!r && gather_rgb) r = ensure_buf(&c->f->g_rgb, c->f->g_rgb_cap, c->nranks * maxpix * 3);
-            if (!r && gather_rgb) r = ensure_buf(&c->f->full_rgb, c->f->full_rgb_cap, 3 * W * Hf);
-        }
-        // (a split ring: each half that size)
-        if (!r) r = F.frame ? ensure_ring(c, (int64_t)FRAME_BLOCK * (c->fanout + 2) * 2 *
-                                                 (frame_split_for(pick_variant(c->mats, c->seq_on ? c->seq : 0).mats) ? 2 : 1))
-                            : ensure_queues(c, (int64_t)batch * npix * c->fanout);
-        if (!r && (int)c->f->ev.size() < F.npass * F.nev) {
-            for (hipEvent_t e : c->f->ev) (void)hipEventDestroy(e);
-            c->f->ev.assign(F.npass * F.nev, nullptr);
-            for (auto& e : c->f->ev)
-                if (hipEventCreate(&e) != hipSuccess) r = fail(SRT_ERR_HIP, "hipEventCreate failed");
-        }
-        // per-pass counters and flags come back through pinned memory once, at the end of the
-        // frame: the passes, the resolve and the output copies are queued without a host round trip
-        if (!r && c->f->host_words < F.npass * F.pass_words + 3) {
-            if (c->f->host) (void)hipHostFree(c->f->host);
-            c->f->host = nullptr;
-            c->f->host_words = 0;
-            if (hipHostMalloc((void**)&c->f->host, (size_t)(F.npass * F.pass_words + 3) * 4, hipHostMallocDefault) !=
-                hipSuccess) {
-                r = fail(SRT_ERR_MEMORY, "pinned host allocation failed");
-            } else {
-                c->f->host_words = F.npass * F.pass_words + 3;  // + shadow count (2), resolve's fx check
-                memset(c->f->host, 0, (size_t)c->f->host_words * 4);  // depths beyond used_words stay zero
-            }
-        }
-        c->f = keep;
-        return r;
-    };
-    if ((rc = ensure_frame(*c->f))) return rc;
-    if (async || c->pipeline) {
-        for (int k = 0; k < c->nslots; ++k) {
-            FrameSlot& other = c->slots[k];
-            if (&other != c->f && other.pending == 0) {
-                if ((rc = ensure_slot(other))) return rc;
-                if ((rc = ensure_frame(other))) return rc;
-            }
-        }
-    }
-    if (use_mt && !c->mt_done) HIP_TRY(hipEventCreateWithFlags(&c->mt_done, hipEventDisableTiming));
-    const Variant& V = pick_variant(c->mats, c->seq_on ? c->seq : 0);
-    // resolve targets: outputs in device memory are written in place by the resolve; host outputs
-    // are resolved into the slot buffers and copied by DMA on the frame's stream (57 GB/s measured
-    // for the ex1 1080p RGB, against 28 GB/s for a resolve kernel storing straight into pinned
-    // memory over PCIe); a shard resolves into its slot tiles (gathered afterwards)
-    const bool rgb_direct = rk == 1, u8_direct = uk == 1;
-    const bool rgb_local = (a->flags & SRT_RENDER_RGB_LOCAL) != 0;
-    double* res_rgb = rgb_local ? c->f->rgb
-                    : sharded ? ((gather_rgb || rgb_rows) ? c->f->rgb : nullptr)
-                              : a->out_rgb ? (rgb_direct ? a->out_rgb : c->f->rgb) : nullptr;
-    const bool rgbx = (a->flags & SRT_RENDER_RGBX) && a->out_srgb8;
-    uint8_t* res_u8 = (sharded || rgbx) ? c->f->u8 : a->out_srgb8 ? (u8_direct ? a->out_srgb8 : c->f->u8) : nullptr;
-    // only the depths this frame can reach are handed back and cleared per pass
-    const int64_t used_words = std::min<int64_t>(F.cnt_words, (int64_t)(F.dcap + 2) * NSHARD);
-    // the numpy stream continues on the device from the previous asynchronous frame (same `mt`)
-    const bool mt_chained = use_mt && async && c->async_pending > 0 && c->mt_chain == a->mt;
-    srt_stats S{};
-    // this frame's first-pass generation already queued by srt_render_prefetch (same stream state,
-    // same frame shape, nothing generated since): not launched again (the first iteration only)
-    // generator width: four waves (one per SIMD) beside the lean fused kernel of the frames in flight
-    c->gen_nt = c->mt_gen_nt_opt ? c->mt_gen_nt_opt
-                                 : ((async && F.fuse && pick_variant(c->mats, c->seq_on ? c->seq : 0).lean != nullptr) ? 256
-                                                                                                          : rtmt_dev::MT_GEN_THREADS);
-    bool pf_hit = false;
-    const int mts = use_mt ? (n_rows >= Hf ? 2 : 0) : 0;
-    const int64_t pf_shape[8] = {W, Hf, a->spp, batch, mt_pm, (int64_t)(c->f - c->slots), mts,
-                                 (int64_t)c->mt_bands_on * 2 + (c->mt_short > 0)};
-    if (prefetch && (F.npass != 1 || !mts)) return SRT_OK;  // (the generation would run on the frame's stream)
-    if (!prefetch && use_mt && pf_in.valid && !async && !sharded && !a->rows && n_rows == Hf && F.npass == 1 && mts &&
-        !memcmp(pf_in.shape, pf_shape, sizeof pf_shape) && pf_in.bt[0] == mt_bt[0] && pf_in.bt[1] == mt_bt[1] &&
-        pf_in.pos == a->mt->pos && !memcmp(pf_in.key, a->mt->key, sizeof pf_in.key))
-        pf_hit = true;
-    for (;;) {
-        if (!prefetch) {
-            if (c->f->pending == 0) clear_host_flags(c, F);  // k_pass_end ORs into them
-            if (c->f->dirty) {
-                HIP_TRY(hipMemsetAsync(c->f->shadow, 0, 8 * NSHARD, c->f->stream));
-                HIP_TRY(hipMemsetAsync(c->f->counts, 0, (size_t)F.cnt_words * 4, c->f->stream));
-                HIP_TRY(hipMemsetAsync(c->f->flags, 0, 8, c->f->stream));
-            }
-            c->f->dirty = true;
-        }
-        int mt_pos = 0;
-        const uint32_t* mt_key = nullptr;
-        // the stream the numpy-stream generation runs on: the MT stream for a single-pass frame
-        // (it waits until the slot's previous frame has read its jitter), else the frame's stream
-        hipStream_t mst = c->f->stream;
-        if (use_mt) {
-            // (auto: whole frames on the high-priority stream, shards on the frame's stream: a stream
-            // shared by the frames serialises their generations, and a shard's band segments -- one
-            // serial generator block each -- are long: a rank of 2's 130k-double bands take ~0.4 ms)
-            if (F.npass == 1 && mts) {
-                if (!c->mt_stream) {
-                    // a high-priority queue (mt_stream 2): the generation's blocks are dispatched ahead
-                    // of the trace kernels' as CUs free up
-                    int lo = 0, hi = 0;
-                    if (mts == 2 && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess)
-                        HIP_TRY(hipStreamCreateWithPriority(&c->mt_stream, hipStreamNonBlocking, hi));
-                    else
-                        HIP_TRY(hipStreamCreateWithFlags(&c->mt_stream, hipStreamNonBlocking));
-                }
-                mst = c->mt_stream;
-                if (c->f->jit_busy && !pf_hit) HIP_TRY(hipStreamWaitEvent(mst, c->f->jit_free, 0));
-            }
-            // this frame's stream starts where the previous frame's ended (device dump window) or at
-            // the caller's state
-            if (c->mt_done && !pf_hit) HIP_TRY(hipStreamWaitEvent(mst, c->mt_done, 0));
-            if (mt_chained) {
-                mt_key = mt_dump(c);
-                mt_pos = c->mt_pos;
-            } else {
-                if (!pf_hit) HIP_TRY(hipMemcpyAsync(mt_key0(c), a->mt->key, rtmt::N * 4, hipMemcpyHostToDevice, mst));
-                mt_key = mt_key0(c);
-                mt_pos = a->mt->pos;
-            }
-        }
-        for (int p = 0; p < F.npass; ++p) {
-            const int s0 = p * batch;
-            const int ns = std::min(batch, a->spp - s0);
-            const int64_t nrays = (int64_t)ns * npix;
-            TraceParams P = base_params(c, a->seed);
-            P.fb = c->f->fb;
-            P.fbx = (c->deterministic && c->fx_ok) ? c->f->fbx : nullptr;
-            P.fb_first = (p == 0);  // the first pass's depth-0 kernel stores the framebuffer (no memset)
-            // sample groups per pixel (k_primary): one (all of the pass's samples in one thread, summed
-            // in registers) unless the frame has too few pixels to fill the GPU -- one GPU's shard of a
-            // multi-GPU frame -- then 2, 4, .. groups on lanes of the pixel's wave (their fixed-point
-            // sums are exact in any grouping: the image does not depend on it).  Enough means one
-            // round of the resident threads for the per-depth kernels (a 1/8 shard of ex1 1080p, 261k
-            // pixels: 6 samples per thread 118 us, 1 sample 133 us) and two for the fused paths, whose
-            // threads trace whole paths (long tails: a 1/8 shard on one group per pixel 0.35 ms, 1.3
-            // rounds, against 0.29 ms on the per-depth kernels)
-            P.pix_groups = pix_groups(c, npix, ns, F.fuse);
-            P.npix = npix;
-            P.cam = *cam;
-            P.cam.xs = c->xs;
-            P.cam.ys = c->ys;
-            P.rows = c->rows;
-            P.sample_base = a->sample_base + s0;
-            P.spp = ns;
-            P.jit_plane = npix;
-            if (use_mt) {
-                // the pass's samples of the whole frame's stream (then the sizing draw after the last
-                // pass); a shard reads its rows by global pixel
-                const int64_t n_out = (int64_t)ns * 4 * W * Hf;
-                const int64_t n_skip = (p + 1 == F.npass) ? 4 * W * Hf : 0;
-                if (p > 0) mt_key = mt_dump(c);  // the previous pass's final window
-                // a pipelined one-pass frame: its final window (the next frame's key) by one jump, so
-                // the next frame's generation starts once this one's jump kernel has run
-                const int64_t n_words = 2 * (n_out + n_skip);
-                const srt_ctx::MtBandTab* bt = mt_bt[p + 1 == F.npass ? 1 : 0];
-                const bool band = bt && rtmt::end_jump(n_words) > 0;
-                const bool end = band || (async && F.npass == 1 && n_words <= (int64_t)rtmt::SEGS * rtmt::L &&
-                                          rtmt::end_jump(n_words) > 0);
-                const uint32_t* end_poly = nullptr;
-                if (end && (rc = mt_end_poly_for(c, n_words, &end_poly))) return rc;
-                // (a pinhole camera reads only the pixel-jitter planes 0 and 1 of each sample)
-                const hipStream_t gst = mst;
-                hipStream_t gen_on = mst;
-                if (pf_hit && p == 0) {  // queued by srt_render_prefetch
-                    mt_pos = pf_in.final_pos;
-                    gen_on = pf_in.gen_on;
-                    c->pf_used++;
-                } else {
-                    if (band) {
-                        if ((rc = mt_launch_bands(c, mst, c->f->mt_win, mt_key, mt_pos, n_words, *bt, c->f->jit, &mt_pos,
-                                                  end_poly, p + 1 == F.npass ? c->mt_done : nullptr, gst,
-                                                  c->f->mt_jumped, &gen_on)))
-                            return rc;
-                    } else if ((rc = mt_launch(c, mst, c->f->mt_win, mt_key, mt_pos, n_out, n_skip, c->f->jit, &mt_pos,
-                                               W * Hf, mt_pm, end_poly, end ? (int64_t)rtmt::end_jump(n_words) : 0,
-                                               end ? c->mt_done : nullptr, gst, c->f->mt_jumped, &gen_on))) {
-                        return rc;
-                    }
-                    // otherwise the next frame's stream may start as soon as this one's is generated
-                    if (p + 1 == F.npass && !end) HIP_TRY(hipEventRecord(c->mt_done, mst));
-                }
-                if (prefetch) {
-                    // queued: the frame's stream waits for it when srt_render comes (a wait queued
-                    // here would also hold up the scene upload's synchronisation of that stream)
-                    srt_ctx::MtPrefetch& q = c->pf;
-                    memcpy(q.key, a->mt->key, sizeof q.key);
-                    q.pos = a->mt->pos;
-                    memcpy(q.shape, pf_shape, sizeof pf_shape);
-                    q.bt[0] = mt_bt[0];
-                    q.bt[1] = mt_bt[1];
-                    q.final_pos = mt_pos;
-                    q.gen_on = gen_on;
-                    q.valid = true;
-                    c->pf_queued++;
-                    return SRT_OK;
-                }
-                if (gen_on != c->f->stream) {
-                    HIP_TRY(hipEventRecord(c->f->jit_ready, gen_on));
-                    HIP_TRY(hipStreamWaitEvent(c->f->stream, c->f->jit_ready, 0));
-                }
-                P.jitter = c->f->jit;
-                P.jit_plane = band ? npix : W * Hf;
-                P.jit_global = band ? 0 : 1;
-            } else if (a->jitter) {
-                const double* src = a->jitter + (int64_t)s0 * 4 * npix;
-                if (jit_dev) {
-                    P.jitter = src;
-                } else {
-                    HIP_TRY(hipMemcpyAsync(c->f->jit, src, (size_t)nrays * 4 * 8, hipMemcpyHostToDevice, c->f->stream));
-                    P.jitter = c->f->jit;
-                }
-            }
-            if (a->out_hit_id) P.hit_out = hit_dev ? a->out_hit_id + (int64_t)s0 * npix : c->f->hit;
-            hipEvent_t* ev = c->f->ev.data() + (int64_t)p * F.nev;
-            if (F.frame) {
-                // the whole pass in one launch: one wave per 64-pixel tile
-                P.ring = c->f->ring;
-                P.ring_lock = c->f->ring_lock;
-                P.ring_cap = c->f->ring_cap;
-                P.nslot = c->f->nslot;
-                P.dcap = F.dcap;
-                P.cnt_out = c->f->counts;
-                P.groups = std::min(F.groups, ns);
-                P.ntiles = (int)ntiles;
-                P.fbg = c->f->fbg;
-                P.fuse_resolve = (F.npass == 1 && F.groups == 1);
-                P.out_rgb = res_rgb;
-                P.out_u8 = res_u8;
-                P.spp_total = a->spp;
-                HIP_TRY(hipEventRecord(ev[0], c->f->stream));
-                hipLaunchKernelGGL(V.frame, dim3((unsigned)(ntiles * P.groups)), dim3(FRAME_BLOCK), lut_bytes(c),
-                                   c->f->stream, P);
-                HIP_TRY(hipGetLastError());
-                if (P.groups > 1) {
-                    hipLaunchKernelGGL(k_fb_groups, dim3(grid_for(3 * npix, c->max_blocks)), dim3(BLOCK), 0, c->f->stream,
-                                       c->f->fb, (const double*)c->f->fbg, P.groups, npix, (int)P.fb_first);
-                    HIP_TRY(hipGetLastError());
-                }
-                HIP_TRY(hipEventRecord(ev[1], c->f->stream));
-                HIP_TRY(hipEventRecord(ev[F.dcap + 1], c->f->stream));
-                if (mst != c->f->stream) {  // the next generation into this slot may start
-                    HIP_TRY(hipEventRecord(c->f->jit_free, c->f->stream));
-                    c->f->jit_busy = true;
-                }
-            } else {
-            // depth 0: raygen fused with the trace step
-            P.depth = 0;
-            P.n_primary = nrays;
-            P.qout = c->f->q[1];
-            P.cnt_out = c->f->counts + NSHARD;
-            P.dcap = F.dcap;
-            HIP_TRY(hipEventRecord(ev[0], c->f->stream));
-            // a single-pass fused frame resolves its pixels in k_primary (no framebuffer)
-            P.fuse_resolve = F.fuse && F.npass == 1;
-            P.out_rgb = res_rgb;
-            P.out_u8 = res_u8;
-            P.spp_total = a->spp;
-            // grid: frames in flight overlap one frame's tail with the next, and fewer, longer blocks
-            // (grid-stride, max_blocks: four rounds of the resident blocks) leave the numpy-stream
-            // generators of the frames behind more room; a synchronous frame has nothing to overlap,
-            // so it takes one block per 256 threads and the hardware fills the tail as blocks finish
-            // (same box, ex1 1080p: the synchronous launch 0.950 -> 0.908 ms; pipelined frames with the
-            // full grid 0.902 -> 0.986 ms, profiles/r05_primary_grid_ab.txt)
-            // the lean kernel of pipelined whole frames (its generators beside it): two blocks per CU,
-            // each grid-striding over ~30 wave iterations of a 1080p frame; the frames in flight fill
-            // the rest of the CU (ex1 1080p: 0.878 ms per frame at 3072 blocks, 0.838 at 512; a rank of
-            // 8's shard, 2025 blocks at most, was slower with it: profiles/r05_lean_grid_ab.txt).  A
-            // pipeline's first frame, with nothing in flight to fill the CUs around its blocks, keeps
-            // the full four rounds (max_blocks).
-            // (option sync_lean: synchronous frames take the lean kernel too -- bench.py times the pipelined
-            // frames' kernel alone that way for its roofline)
-            const bool lean = F.fuse && (async || c->sync_lean) && V.lean;
-            if (lean) c->lean_launches++;
-            const int pgrid = !async ? INT_MAX
-                                     : (!lean || c->async_pending == 0               ? c->max_blocks
-                                        : n_rows == Hf && c->lean_blocks > 0              ? c->lean_blocks
-                                        : n_rows < Hf && c->lean_blocks_shard > 0         ? c->lean_blocks_shard
-                                                                                            : c->max_blocks);
-            hipLaunchKernelGGL(F.fuse ? (lean ? (c->lane_stats && V.lean_stats ? V.lean_stats : V.lean) : V.fused) : V.primary,
-                               dim3(grid_for(((npix * P.pix_groups + 63) / 64) * 64, pgrid)), dim3(BLOCK),
-                               lut_bytes(c), c->f->stream, P);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(ev[1], c->f->stream));
-            if (F.fuse)  // every depth traced: the deeper depths' events mark the same point
-                for (int d = 1; d <= F.dcap; ++d) HIP_TRY(hipEventRecord(ev[1 + d], c->f->stream));
-            if (mst != c->f->stream) {  // the next generation into this slot may start
-                HIP_TRY(hipEventRecord(c->f->jit_free, c->f->stream));
-                c->f->jit_busy = true;
-            }
-            P.fb_first = 0;
-            for (int d = 1; d <= F.dcap && !F.fuse; ++d) {
-                if (F.chain_from > 0 && d > F.chain_from) break;  // traced by the chain kernel
-                P.depth = d;
-                P.qin = c->f->q[d & 1];
-                P.qout = c->f->q[(d + 1) & 1];
-                P.cnt_in = c->f->counts + (int64_t)d * NSHARD;
-                P.cnt_out = c->f->counts + (int64_t)(d + 1) * NSHARD;
-                P.chain = (d == F.chain_from);
-                P.dcap = F.dcap;
-                hipLaunchKernelGGL(P.chain ? V.chain : V.trace, dim3(trace_grid(c)), dim3(BLOCK),
-                                   lut_bytes(c), c->f->stream, P);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipEventRecord(ev[1 + d], c->f->stream));
-            }
-            }
-            uint32_t* hp = c->f->host + p * F.pass_words;
-            // counters of this pass -> pinned host words [0, used_words) (the unused depths are zero
-            // on the host), flags OR-ed into the two words at [cnt_words, cnt_words + 2); the last
-            // pass's are handed over by k_resolve
-            if (p + 1 < F.npass) {
-                hipLaunchKernelGGL(k_pass_end, dim3(1), dim3(BLOCK), 0, c->f->stream, c->f->counts, used_words, c->f->flags,
-                                   hp, hp + F.cnt_words);
-                HIP_TRY(hipGetLastError());
-            }
-            if (a->out_hit_id && !hit_dev)
-                HIP_TRY(hipMemcpyAsync(a->out_hit_id + (int64_t)s0 * npix, c->f->hit, (size_t)nrays * 4,
-                                       hipMemcpyDeviceToHost, c->f->stream));
-        }
-        if (use_mt) c->mt_pos = mt_pos;
-        uint32_t* hshadow = c->f->host + F.npass * F.pass_words;
-        // (a single-pass frame kernel or fused frame has resolved its pixels: k_resolve only hands over
-        // the counters and the shadow count)
-        const bool fused = F.npass == 1 && ((F.frame && F.groups == 1) || F.fuse);
-        uint32_t* hlast = c->f->host + (F.npass - 1) * F.pass_words;
-        hipLaunchKernelGGL(k_resolve, dim3(fused ? 1 : grid_for(npix, c->max_blocks)), dim3(BLOCK), 0, c->f->stream, c->f->fb,
-                           (F.frame || !c->deterministic || !c->fx_ok) ? nullptr
-                                                                       : (const unsigned long long*)c->f->fbx,
-                           fused ? (int64_t)0 : npix, c->f->shadow, hshadow, (double)a->spp, res_rgb, res_u8, c->f->counts,
-                           used_words, c->f->flags, hlast, hlast + F.cnt_words);
-        HIP_TRY(hipGetLastError());
-        c->f->dirty = false;  // the kernels above leave counts/flags/shadow zeroed
-        // this rank's rows of the linear RGB into the shared host frame: per plane, the rank's band j
-        // at frame band j n + rank, one pitched copy of the full bands, then a short last band
-        if (rgb_rows) {
-            const int64_t band_px = band * W;
-            const int64_t nb = npix / band_px, tail = npix - nb * band_px;
-            for (int pl = 0; pl < 3; ++pl) {
-                double* dst = a->out_rgb + (int64_t)pl * W * Hf;
-                const double* src = c->f->rgb + (int64_t)pl * npix;
-                if (nb > 0)
-                    HIP_TRY(hipMemcpy2DAsync(dst + (int64_t)c->rank * band_px, (size_t)(c->nranks * band_px * 8), src,
-                                             (size_t)(band_px * 8), (size_t)(band_px * 8), (size_t)nb,
-                                             hipMemcpyDeviceToHost, c->f->stream));
-                if (tail > 0) {
-                    // (the rank's band nb, in period nb)
-                    const int64_t bt = nb * c->nranks + c->rank;
-                    HIP_TRY(hipMemcpyAsync(dst + bt * band_px, src + nb * band_px, (size_t)(tail * 8),
-                                           hipMemcpyDeviceToHost, c->f->stream));
-                }
-            }
-        }
-        // the shard's tiles to rank 0 (RCCL over xGMI), assembled into the frame there
-        FrameSlot::Gather& G = c->f->gather;
-        G = FrameSlot::Gather{};
-        if (sharded) {
-            G.on = true;
-            G.W = W;
-            G.H = Hf;
-            G.npix = npix;
-            G.maxpix = maxpix;
-            G.band = band;
-            G.want_u8 = true;
-            G.want_rgb = gather_rgb;
-            if (c->rank == 0) {
-                G.dst_u8 = (a->out_srgb8 && u8_dev) ? a->out_srgb8 : c->f->full_u8;
-                G.dst_rgb = (a->out_rgb && rgb_dev) ? a->out_rgb : c->f->full_rgb;
-                G.host_u8 = (a->out_srgb8 && !u8_dev) ? a->out_srgb8 : nullptr;
-                G.host_rgb = (a->out_rgb && !rgb_dev && gather_rgb) ? a->out_rgb : nullptr;
-            }
-        }
-        const uint8_t* u8_src = c->f->u8;
-        int64_t u8_bytes = 3 * npix;
-        if (reh_n) {
-            GatherTiles T{};
-            for (int q = 0; q < reh_n; ++q) {
-                T.u8[q] = q == 0 ? c->f->u8 : c->f->g_u8 + (int64_t)q * reh_maxpix * 3;
-                T.npix[q] = shard_rank_rows(Hf, reh_n, q, reh_band) * W;
-            }
-            hipLaunchKernelGGL(k_assemble, dim3(grid_for(W * Hf, c->max_blocks)), dim3(BLOCK), 0, c->f->stream, T, reh_n,
-                               reh_band, W, Hf, c->f->full_u8, (double*)nullptr);
-            HIP_TRY(hipGetLastError());
-            u8_src = c->f->full_u8;
-            u8_bytes = 3 * W * Hf;
-        }
-        if (rgbx) {
-            uint32_t* dst4 = reinterpret_cast<uint32_t*>(u8_direct ? a->out_srgb8 : c->f->full_u8);
-            hipLaunchKernelGGL(k_rgbx, dim3(grid_for(npix, c->max_blocks)), dim3(BLOCK), 0, c->f->stream, c->f->u8, dst4,
-                               npix);
-            HIP_TRY(hipGetLastError());
-            u8_src = c->f->full_u8;
-            u8_bytes = 4 * npix;
-        }
-        if (async) {
-            // (a synchronous frame gathers after its retries: every rank gathers each frame once)
-            if (sharded && !c->defer_gather && (rc = gather_frame(c))) return rc;
-            if (!sharded && ((a->out_srgb8 && !u8_direct) || (a->out_rgb && !rgb_direct))) {
-                hipStream_t cs = c->f->stream;
-                if (a->out_srgb8 && !u8_direct)
-                    HIP_TRY(hipMemcpyAsync(a->out_srgb8, u8_src, (size_t)u8_bytes, hipMemcpyDeviceToHost, cs));
-                if (a->out_rgb && !rgb_direct)
-                    HIP_TRY(hipMemcpyAsync(a->out_rgb, c->f->rgb, (size_t)3 * npix * 8, hipMemcpyDeviceToHost, cs));
-            }
-            // host outputs (pinned) are copied on the frame's stream; stats and errors come with
-            // srt_render_finish; the next asynchronous frame goes to the next slot
-            if (use_mt) c->mt_chain = a->mt;
-            c->async_pending++;
-            c->f->pending++;
-            c->f->plan = F;
-            c->last_slot = (int)(c->f - c->slots);
-            c->next_slot = (c->last_slot + 1) % c->nslots;
-            return SRT_OK;
-        }
-        if (!sharded && a->out_rgb && !rgb_direct)
-            HIP_TRY(hipMemcpyAsync(a->out_rgb, c->f->rgb, (size_t)3 * npix * 8, hipMemcpyDeviceToHost, c->f->stream));
-        if (!sharded && a->out_srgb8 && !u8_direct)
-            HIP_TRY(hipMemcpyAsync(a->out_srgb8, u8_src, (size_t)u8_bytes, hipMemcpyDeviceToHost, c->f->stream));
-        c->f->dirty = true;
-        HIP_TRY(hipStreamSynchronize(c->f->stream));
-        c->f->dirty = false;
-        const int64_t retries = S.retries;
-        uint32_t bits = 0;
-        rc = collect_frame(c, F, S, &bits);
-        if (rc == SRT_RETRY) {
-            // render the frame again: without chain mode after a tie gave a chained ray a second
-            // child (the same tie would recur), with bigger queues after an overflow
-            S.retries = retries + 1;
-            if (S.retries > 8) return fail(SRT_ERR_MEMORY, "ray queues keep overflowing");
-            if (bits & RETRY_CHAIN_TIE) {
-                F.chain_from = 0;
-                F.fuse = false;
-            }
-            if ((bits & RETRY_OVERFLOW) &&
-                (rc = F.frame ? ensure_ring(c, 2 * c->f->ring_cap) : ensure_queues(c, 2 * c->f->seg * NSHARD)))
-                return rc;
-            pf_hit = false;  // (the retry generates its stream again from the caller's state)
-            continue;
-        }
-        S.retries = retries;
-        if (rc) return rc;
-        break;
-    }
-    if (sharded && !c->defer_gather) {
-        if ((rc = gather_frame(c))) return rc;
-        HIP_TRY(hipStreamSynchronize(c->f->stream));
-    }
-    if (use_mt) {  // numpy's state after this frame's draws
-        HIP_TRY(hipMemcpy(a->mt->key, mt_dump(c), rtmt::N * 4, hipMemcpyDeviceToHost));
-        a->mt->pos = c->mt_pos;
-    }
-    if (st) {
-        S.ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-        *st = S;
-    }
-    return SRT_OK;
-}
-}  // namespace
+#include "rt_render.h"  // render_impl: srt_render and srt_render_prefetch
 
 extern "C" {
 int srt_render(srt_ctx* c, const srt_camera* cam, const srt_render_args* a, srt_stats* st) {
@@ -3663,7 +2963,7 @@ int trace_impl(srt_ctx* c, const srt_trace_args* a, const int32_t* fid, const do
     }
     if ((rc = ensure_buf(&c->f->fb, c->f->fb_cap, 3 * n))) return rc;
     if ((rc = ensure_buf(&c->f->fbx, c->f->fbx_cap, fx_words(n)))) return rc;
-    if ((rc = ensure_queues(c, n * c->fanout))) return rc;
+    if ((rc = ensure_queues(*c->f, n * c->fanout))) return rc;
     // depths a->depth .. a->depth + cap (the batch's depth is a scalar in the reference)
     const int d0 = a->depth;
     const int dlast = kids ? d0 : std::min(SRT_MAX_DEPTHS - 2, d0 + depth_cap(c));
@@ -3684,7 +2984,7 @@ int trace_impl(srt_ctx* c, const srt_trace_args* a, const int32_t* fid, const do
         hipLaunchKernelGGL(k_seed_queue, dim3(grid_for(n, c->max_blocks)), dim3(BLOCK), 0, c->f->stream, c->f->q[d0 & 1],
                            c->f->seg, O, D, med, n, (uint32_t)d0, (uint32_t)a->diffuse_reflections, (uint32_t)c->S.nmedia);
         HIP_TRY(hipGetLastError());
-        TraceParams P = base_params(c, a->seed);
+        TraceParams P = base_params(c, *c->f, a->seed);
         P.fb = c->f->fb;
         P.fbx = fx ? c->f->fbx : nullptr;
         P.npix = n;
@@ -3725,7 +3025,7 @@ int trace_impl(srt_ctx* c, const srt_trace_args* a, const int32_t* fid, const do
         if (flags[1]) {
             S.retries++;
             if (flags[1] & RETRY_FIXED_RANGE) fx = false;  // again with f64 atomics
-            if ((flags[1] & RETRY_OVERFLOW) && (rc = ensure_queues(c, 2 * c->f->seg * NSHARD))) break;
+            if ((flags[1] & RETRY_OVERFLOW) && (rc = ensure_queues(*c->f, 2 * c->f->seg * NSHARD))) break;
             continue;
         }
         if (!kids && depth_total(counts.data() + (int64_t)(dlast + 1) * NSHARD, c->f->seg) != 0) {
@@ -4173,6 +3473,45 @@ int srt_comm_rank(srt_ctx* c, int* nranks, int* rank) {
 }  // extern "C"
 static int render_group_once(srt_ctx** ctxs, int n, const srt_camera* cam, const srt_render_args* a, srt_stats* st);
 static int render_group_async(srt_ctx** ctxs, int n, const srt_camera* cam, const srt_render_args* a);
+
+// The gathers of all the group's contexts posted in one RCCL group, then the frame assembled on rank 0
+static int gather_group(srt_ctx** ctxs, int n) {
+    int rc = SRT_OK;
+    if (n > 1) {
+        ncclResult_t r = ncclGroupStart();
+        for (int q = 0; q < n && !rc && r == ncclSuccess; ++q) {
+            (void)hipSetDevice(ctxs[q]->device);
+            rc = gather_post(ctxs[q]);
+        }
+        ncclResult_t r2 = ncclGroupEnd();
+        if (!rc && (r != ncclSuccess || r2 != ncclSuccess))
+            rc = fail(SRT_ERR_HIP, std::string("RCCL group gather: ") + ncclGetErrorString(r != ncclSuccess ? r : r2));
+    }
+    if (!rc) {
+        (void)hipSetDevice(ctxs[0]->device);
+        rc = gather_finish(ctxs[0]);
+    }
+    return rc;
+}
+
+// srt_render_finish on every context (whatever `rc` the frame had so far: no rank is left with frames
+// in flight); `sum`: rank 0's stats with the ray counts of all ranks.  Returns the first error.
+static int finish_group(srt_ctx** ctxs, int n, srt_stats& sum, int rc) {
+    for (int q = 0; q < n; ++q) {
+        srt_stats sq{};
+        const int r = srt_render_finish(ctxs[q], &sq);
+        if (!rc) rc = r;
+        if (q == 0) {
+            sum = sq;
+        } else {
+            for (int d = 0; d < SRT_MAX_DEPTHS; ++d) sum.rays_per_depth[d] += sq.rays_per_depth[d];
+            sum.total_rays += sq.total_rays;
+            sum.shadow_rays += sq.shadow_rays;
+            sum.n_depths = std::max(sum.n_depths, sq.n_depths);
+        }
+    }
+    return rc;
+}
 extern "C" {
 
 int srt_render_group(srt_ctx** ctxs, int n, const srt_camera* cam, const srt_render_args* a, srt_stats* st) {
@@ -4224,34 +3563,10 @@ static int render_group_once(srt_ctx** ctxs, int n, const srt_camera* cam, const
         rc = srt_render(ctxs[q], cam, &aq, nullptr);
     }
     FrameSlot* f0 = ctxs[0]->f;
-    if (!rc && n > 1) {
-        ncclResult_t r = ncclGroupStart();
-        for (int q = 0; q < n && !rc && r == ncclSuccess; ++q) {
-            (void)hipSetDevice(ctxs[q]->device);
-            rc = gather_post(ctxs[q]);
-        }
-        ncclResult_t r2 = ncclGroupEnd();
-        if (!rc && (r != ncclSuccess || r2 != ncclSuccess))
-            rc = fail(SRT_ERR_HIP, std::string("RCCL group gather: ") + ncclGetErrorString(r != ncclSuccess ? r : r2));
-    }
-    if (!rc) {
-        (void)hipSetDevice(ctxs[0]->device);
-        rc = gather_finish(ctxs[0]);
-    }
+    if (!rc) rc = gather_group(ctxs, n);
+    for (int q = 0; q < n; ++q) ctxs[q]->defer_gather = false;
     srt_stats sum{};
-    for (int q = 0; q < n; ++q) {
-        ctxs[q]->defer_gather = false;
-        srt_stats sq{};
-        int r = srt_render_finish(ctxs[q], &sq);
-        if (!rc) rc = r;
-        if (q == 0) sum = sq;
-        else {
-            for (int d = 0; d < SRT_MAX_DEPTHS; ++d) sum.rays_per_depth[d] += sq.rays_per_depth[d];
-            sum.total_rays += sq.total_rays;
-            sum.shadow_rays += sq.shadow_rays;
-            sum.n_depths = std::max(sum.n_depths, sq.n_depths);
-        }
-    }
+    rc = finish_group(ctxs, n, sum, rc);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(ctxs[0]->device));
     const int64_t np = (int64_t)cam->width * cam->height;
@@ -4281,20 +3596,7 @@ static int render_group_async(srt_ctx** ctxs, int n, const srt_camera* cam, cons
         rc = srt_render(ctxs[q], cam, &aq, nullptr);
         if (!rc) ++queued;
     }
-    if (!rc && n > 1) {
-        ncclResult_t r = ncclGroupStart();
-        for (int q = 0; q < n && !rc && r == ncclSuccess; ++q) {
-            (void)hipSetDevice(ctxs[q]->device);
-            rc = gather_post(ctxs[q]);
-        }
-        ncclResult_t r2 = ncclGroupEnd();
-        if (!rc && (r != ncclSuccess || r2 != ncclSuccess))
-            rc = fail(SRT_ERR_HIP, std::string("RCCL group gather: ") + ncclGetErrorString(r != ncclSuccess ? r : r2));
-    }
-    if (!rc) {
-        (void)hipSetDevice(ctxs[0]->device);
-        rc = gather_finish(ctxs[0]);
-    }
+    if (!rc) rc = gather_group(ctxs, n);
     for (int q = 0; q < n; ++q) ctxs[q]->defer_gather = false;
     if (rc && queued < n) {
         // a context refused the frame: the others' shards are queued without the gather; wait for them
@@ -4308,21 +3610,8 @@ extern "C" {
 
 int srt_render_group_finish(srt_ctx** ctxs, int n, srt_stats* st) {
     if (!ctxs || n < 1) return fail(SRT_ERR_ARG, "null argument");
-    int rc = SRT_OK;
     srt_stats sum{};
-    for (int q = 0; q < n; ++q) {
-        srt_stats sq{};
-        const int r = srt_render_finish(ctxs[q], &sq);
-        if (!rc) rc = r;
-        if (q == 0) {
-            sum = sq;
-        } else {
-            for (int d = 0; d < SRT_MAX_DEPTHS; ++d) sum.rays_per_depth[d] += sq.rays_per_depth[d];
-            sum.total_rays += sq.total_rays;
-            sum.shadow_rays += sq.shadow_rays;
-            sum.n_depths = std::max(sum.n_depths, sq.n_depths);
-        }
-    }
+    const int rc = finish_group(ctxs, n, sum, SRT_OK);
     if (st && !rc) *st = sum;
     return rc;
 }

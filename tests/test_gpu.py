@@ -391,6 +391,57 @@ def test_gpu_async_frames_match_sync_frame():
     assert np.array_equal(u8.reshape(120, 160, 3), ref.srgb8)
 
 
+def test_gpu_async_frames_of_mixed_shapes_match_sync_frames():
+    """Asynchronous frames of different shapes queued back to back, with no finish in between: a
+    small frame, a larger one (its slot's buffers must grow), the small one again (fits what is
+    there), and one of three passes (more events and pinned words).  Whether a frame may be queued
+    behind the frames in flight or must first wait for them to grow a buffer, each equals the
+    synchronous render of the same arguments bit for bit."""
+    import ctypes
+    from sightpy import _native as N
+
+    B = _backend()
+    # (width, height, spp, batch_spp)
+    frames = [(48, 36, 2, 0), (96, 72, 2, 0), (48, 36, 2, 0), (48, 36, 5, 2)]
+    np.random.seed(11)
+    scs, jits, refs = [], [], []
+    for w, h, spp, batch in frames:
+        sc = scenes.example1(w, h, 4)
+        jit = np.ascontiguousarray(sc.camera.draw_jitter(spp))
+        scs.append(sc)
+        jits.append(jit)
+        refs.append(B.render_scene(sc, spp, jitter=jit, seed=5, batch_size=batch or None))
+    lib, ctx = B.context()
+    outs = []
+    for k, (w, h, spp, batch) in enumerate(frames):
+        npix = w * h
+        dj = B.device_buffer("test_mixed_jit%d" % k, jits[k].nbytes)
+        N.check(lib, lib.srt_memcpy(ctx, dj, N.ptr(jits[k]), jits[k].nbytes))
+        outs.append((dj, B.device_buffer("test_mixed_rgb%d" % k, 3 * npix * 8),
+                     B.device_buffer("test_mixed_u8%d" % k, 3 * npix)))
+    try:
+        for k, (w, h, spp, batch) in enumerate(frames):
+            a = N.RenderArgs()
+            a.spp, a.sample_base, a.n_rows, a.batch_spp = spp, 0, h, batch
+            a.jitter, a.seed, a.out_rgb, a.out_srgb8, a.out_hit_id = outs[k][0], 5, outs[k][1], outs[k][2], None
+            a.flags = N.RENDER_ASYNC
+            cd = B.camera_desc(scs[k].camera)
+            N.check(lib, lib.srt_render(ctx, ctypes.byref(cd), ctypes.byref(a), None))
+        N.check(lib, lib.srt_render_finish(ctx, None))
+        for k, (w, h, spp, batch) in enumerate(frames):
+            npix = w * h
+            rgb = np.empty((3, npix))
+            u8 = np.empty((npix, 3), dtype=np.uint8)
+            N.check(lib, lib.srt_memcpy(ctx, N.ptr(rgb), outs[k][1], rgb.nbytes))
+            N.check(lib, lib.srt_memcpy(ctx, N.ptr(u8), outs[k][2], u8.nbytes))
+            assert np.array_equal(rgb, refs[k].rgb), "frame %d: linear RGB" % k
+            assert np.array_equal(u8.reshape(h, w, 3), refs[k].srgb8), "frame %d: uint8 image" % k
+    finally:
+        for k in range(len(frames)):
+            for name in ("jit", "rgb", "u8"):
+                B.release_buffer("test_mixed_%s%d" % (name, k))
+
+
 def test_gpu_frames_are_bit_reproducible():
     """The reference is deterministic; so are these frames: depth-0 colours are summed in the pixel's
     own thread and every other contribution goes into an order-independent fixed-point sum, so
