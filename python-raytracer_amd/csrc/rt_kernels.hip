@@ -1,22 +1,29 @@
-// rt_kernels.hip -- gfx950 wavefront tracer behind the C ABI of include/sightpy_rt.h.
+// rt_kernels.hip -- gfx950 ray tracer behind the C ABI of include/sightpy_rt.h: the one translation
+// unit of libsightpy_hip.so (rt_render.h, the host side of srt_render, is included below).
 //
-// The reference (sightpy) recursively evaluates numpy batches: intersect every collider, reduce
-// the nearest hit, compact the rays per collider, shade, recurse (ray.py:122-148).  Here the
-// recursion is flattened into a breadth-first wavefront over structure-of-arrays ray queues in
-// HBM, one launch per depth:
+// The reference (sightpy) recursively evaluates numpy batches: intersect every collider, reduce the
+// nearest hit, compact the rays per collider, shade, recurse (ray.py:122-148).  A colour composes
+// linearly along the ray tree (colour = local + F * child), so every ray carries the product of the
+// weights above it (its throughput) and its contribution is summed into the per-pixel framebuffer,
+// in order-independent fixed-point sums by default (f64 atomics otherwise).  A frame takes one of
+// three kernel paths (RenderCall::plan_frame in rt_render.h chooses; all three share trace_one):
 //
-//   k_primary      depth 0: primary-ray generation (camera.py:51-85) fused with the trace step,
-//                  one thread per pixel looping over the pass's samples
-//   k_trace        depth d: read ray d from queue, nearest hit over all colliders, shade,
-//                  add throughput * local colour to the framebuffer, append children to d+1
-//   k_resolve      spp average + sRGB + intensity clip + uint8 (scene.py:118-140)
+//   per-depth    k_primary generates the primary rays (camera.py:51-85) and traces depth 0; one k_trace
+//                launch per deeper depth reads ray queue d in HBM (structure of arrays, sharded append
+//                counters) and appends the children to queue d + 1.  In chain mode the k_trace of a
+//                thinly populated depth follows each ray's single-child chain to its end.  srt_trace and
+//                the shade levels seed the queues from the caller's rays and run this path.
+//   fused, lean  single-child scenes: k_primary<.., FUSE> traces a pixel's whole path in its thread, no
+//                queue; k_primary_lean is the same body under a register cap for pipelined frames,
+//                which leaves room for the next frame's numpy-stream generators beside it.
+//   k_frame      scenes whose rays branch (refractive, thin-film, diffuse fan-out): one wave per
+//                64-pixel tile traces the whole pass, its children in a per-wave ring in HBM; a
+//                single-pass frame resolves its pixels in the kernel.
 //
-// A colour composes linearly along the ray tree (colour = local + F * child), so each queued ray
-// carries the product of the weights above it (its throughput) and contributions are summed into
-// the per-pixel framebuffer with float64 atomics.  Scene tables are read through wave-uniform
-// indices (scalar loads) in the collider loop; shading runs as a waterfall over the materials
-// present in a wave so each material's parameters are wave-uniform too.  Children are appended
-// with one block-wide exclusive scan and one atomicAdd per block.
+// Scene tables are read through wave-uniform indices (scalar loads) in the collider loop; shading runs
+// as a waterfall over the materials present in a wave.  k_resolve (spp average + sRGB + intensity clip
+// + uint8, scene.py:118-140) ends a frame that did not resolve itself.  Device memory is owned by
+// DevBuf (one allocation with a capacity) and DevList (allocations released together).
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -30,6 +37,7 @@
 #include <string>
 #include <thread>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "rt_bvh.h"
@@ -1468,14 +1476,66 @@ hipError_t dalloc(T** p, int64_t count) {
     return hipMalloc((void**)p, (size_t)std::max<int64_t>(count, 1) * sizeof(T));
 }
 
-// Device buffers of one API call, freed on every exit path (the early HIP_TRY returns included)
-struct CallBufs {
+// One device allocation of `cap` elements, released with its owner.  Converts to the plain pointer,
+// so kernels' arguments and HIP calls take it as they take a T*.
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    int64_t cap = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            (void)reset();
+            p = o.p, cap = o.cap;
+            o.p = nullptr, o.cap = 0;
+        }
+        return *this;
+    }
+    ~DevBuf() { (void)reset(); }
+    operator T*() const { return p; }
+    hipError_t reset() {
+        const hipError_t e = p ? hipFree(p) : hipSuccess;
+        p = nullptr;
+        cap = 0;
+        return e;
+    }
+    // room for `count` elements: grows only, and a buffer that grows loses its contents
+    int ensure(int64_t count) {
+        if (count <= cap && p) return SRT_OK;
+        (void)reset();
+        if (dalloc(&p, count) != hipSuccess) return fail(SRT_ERR_MEMORY, "device allocation failed");
+        cap = count;
+        return SRT_OK;
+    }
+};
+// a fixed buffer, allocated once
+template <typename T>
+hipError_t dalloc(DevBuf<T>* b, int64_t count) {
+    (void)b->reset();
+    const hipError_t e = dalloc(&b->p, count);
+    if (e == hipSuccess) b->cap = count;
+    return e;
+}
+
+// Device allocations made and released together: the buffers of one API call (freed on every exit
+// path, the early HIP_TRY returns included), a scene's tables, a slot's queues or rings
+struct DevList {
     std::vector<void*> p;
-    CallBufs() = default;
-    CallBufs(const CallBufs&) = delete;
-    CallBufs& operator=(const CallBufs&) = delete;
-    ~CallBufs() {
+    DevList() = default;
+    DevList(DevList&& o) noexcept : p(std::move(o.p)) { o.p.clear(); }
+    DevList& operator=(DevList&& o) noexcept {
+        if (this != &o) {
+            clear();
+            p = std::move(o.p);
+            o.p.clear();
+        }
+        return *this;
+    }
+    ~DevList() { clear(); }
+    void clear() {
         for (void* b : p) (void)hipFree(b);
+        p.clear();
     }
     template <typename T>
     hipError_t alloc(T** out, int64_t count) {
@@ -1483,6 +1543,19 @@ struct CallBufs {
         const hipError_t e = dalloc(out, count);
         if (e == hipSuccess) p.push_back(*out);
         return e;
+    }
+    // an input of a call: `count` elements of `src` in a buffer of their own, copied on `st` (without
+    // one, before the call returns)
+    template <typename T>
+    hipError_t in(T** out, const T* src, int64_t count, hipStream_t st = nullptr) {
+        const hipError_t e = alloc(out, count);
+        return e != hipSuccess ? e : copy(*out, src, count, st);
+    }
+    // `count` elements of an output back to the caller's `dst`
+    template <typename T>
+    static hipError_t copy(T* dst, const T* src, int64_t count, hipStream_t st = nullptr) {
+        const size_t bytes = (size_t)count * sizeof(T);
+        return st ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, st) : hipMemcpy(dst, src, bytes, hipMemcpyDefault);
     }
 };
 
@@ -1557,48 +1630,36 @@ struct FrameSlot {
     hipEvent_t jit_free = nullptr;   // recorded on `stream` after the last kernel that reads the jitter
     hipEvent_t mt_jumped = nullptr;  // recorded on the MT stream after this slot's jump kernel
     bool jit_busy = false;           // `jit_free` guards the jitter buffer
-    uint32_t* mt_win = nullptr;      // segment windows of this slot's numpy-stream generation
-    int64_t mt_win_cap = 0;
+    DevBuf<uint32_t> mt_win;         // segment windows of this slot's numpy-stream generation
     // ray queues: 2 x NSHARD segments of `seg` rays
     Queue q[2]{};
     int64_t seg = 0;
-    std::vector<void*> queue_bufs;
+    DevList queue_bufs;
     // frame kernel rings (k_frame): nslot rings of ring_cap rays, one lock word per ring
     Queue ring{};
     int64_t ring_cap = 0;
     int nslot = 0;
-    uint32_t* ring_lock = nullptr;
-    std::vector<void*> ring_bufs;
+    uint32_t* ring_lock = nullptr;  // (in ring_bufs)
+    DevList ring_bufs;
     // frame buffers
-    double* fb = nullptr;
-    int64_t fb_cap = 0;
-    double* fbg = nullptr;  // k_frame sample groups' partial sums [groups][3][npix]
-    int64_t fbg_cap = 0;
-    unsigned long long* fbx = nullptr;  // [3][npix] fixed-point sums + [npix] f32 magnitudes (fb_add)
-    int64_t fbx_cap = 0;
-    double* rgb = nullptr;
-    int64_t rgb_cap = 0;
-    uint8_t* u8 = nullptr;
-    int64_t u8_cap = 0;
-    double* jit = nullptr;
-    int64_t jit_cap = 0;
-    int32_t* hit = nullptr;
-    int64_t hit_cap = 0;
-    uint32_t* counts = nullptr;  // [SRT_MAX_DEPTHS][NSHARD]
-    uint32_t* flags = nullptr;   // [2]
-    unsigned long long* shadow = nullptr;  // [NSHARD]
+    DevBuf<double> fb;
+    DevBuf<double> fbg;  // k_frame sample groups' partial sums [groups][3][npix]
+    DevBuf<unsigned long long> fbx;  // [3][npix] fixed-point sums + [npix] f32 magnitudes (fb_add)
+    DevBuf<double> rgb;
+    DevBuf<uint8_t> u8;
+    DevBuf<double> jit;
+    DevBuf<int32_t> hit;
+    DevBuf<uint32_t> counts;  // [SRT_MAX_DEPTHS][NSHARD]
+    DevBuf<uint32_t> flags;   // [2]
+    DevBuf<unsigned long long> shadow;  // [NSHARD]
     std::vector<hipEvent_t> ev;
     uint32_t* host = nullptr;  // pinned: per-pass counters/flags, shadow count
     int64_t host_words = 0;
     // SRT_RENDER_SHARDED on rank 0: every rank's tiles (padded to the largest shard) and the frame
-    uint8_t* g_u8 = nullptr;
-    int64_t g_u8_cap = 0;
-    double* g_rgb = nullptr;
-    int64_t g_rgb_cap = 0;
-    uint8_t* full_u8 = nullptr;
-    int64_t full_u8_cap = 0;
-    double* full_rgb = nullptr;
-    int64_t full_rgb_cap = 0;
+    DevBuf<uint8_t> g_u8;
+    DevBuf<double> g_rgb;
+    DevBuf<uint8_t> full_u8;
+    DevBuf<double> full_rgb;
     // the frame's gather (srt_render_group posts it for all its contexts in one RCCL group)
     struct Gather {
         bool on = false;
@@ -1636,9 +1697,9 @@ struct srt_ctx {
     std::vector<uint8_t> col_hit_albedo;
     int n_user_lights = 0;
     bool needs_inputs = false;
-    std::vector<void*> scene_bufs;
+    DevList scene_bufs;
     // texel pool (outside scene_bufs: survives re-uploads with the same texel_key)
-    uint8_t* texels = nullptr;
+    DevBuf<uint8_t> texels;
     uint64_t texel_key = 0;
     int64_t texel_bytes = 0;
     uint64_t texel_layout = 0;  // hash of the pool layout the records' offsets were remapped to
@@ -1646,15 +1707,13 @@ struct srt_ctx {
     // option "mt_jump_parts": blocks per jump window (0: mt_jump_parts's choice)
     int mt_parts_opt = 0;
     // camera tables (shared by the slots; uploaded only when they change)
-    double* xs = nullptr;
-    double* ys = nullptr;
-    int32_t* rows = nullptr;
-    int64_t cam_cap[3] = {0, 0, 0};
+    DevBuf<double> xs, ys;
+    DevBuf<int32_t> rows;
     std::vector<uint8_t> cam_host[3];  // host copies of what xs / ys / rows hold
-    uint32_t* mt = nullptr;    // MT19937 jump tables (255 x 624), two round keys, two final windows
+    DevBuf<uint32_t> mt;  // MT19937 jump tables (255 x 624), two round keys, two final windows
     // the y words (k_mt_y) of a generation's key: [0] / [1] those of the two final windows (made
     // by the end block that made the window, valid flag per window), [2] scratch for other keys
-    uint32_t* mt_y = nullptr;
+    DevBuf<uint32_t> mt_y;
     bool mt_y_valid[2] = {false, false};
     // band mode (a shard's rows of the numpy stream, rt_mt_kernel.h MtArgs::bands): per pass shape,
     // the segment list and its jump polynomials (host-made once, kept for the context's life)
@@ -1663,11 +1722,11 @@ struct srt_ctx {
         uint64_t rows_hash;
         int nseg;
         int64_t band_len, band_period;  // merged segments store k % band_period < band_len (doubles)
-        int64_t* bands;   // device [nseg][4]
-        uint32_t* polys;  // device [nseg][624]
+        DevBuf<int64_t> bands;   // [nseg][4]
+        DevBuf<uint32_t> polys;  // [nseg][624]
     };
     std::deque<MtBandTab> mt_bandtabs;  // (stable addresses: frames hold pointers into it)
-    std::vector<std::pair<int64_t, uint32_t*>> mt_end_polys;  // frame-end jump polynomial per word count
+    std::vector<std::pair<int64_t, DevBuf<uint32_t>>> mt_end_polys;  // frame-end jump polynomial per word count
     bool mt_bands_on = true;  // option "mt_bands"
     // option "mt_short": doubles per segment of a whole frame's stream when nothing else is in flight
     // (a synchronous frame -- Scene.render -- or the first of a pipeline): its generation cannot hide
@@ -1681,8 +1740,7 @@ struct srt_ctx {
     // split: same box, ex1 1080p pipelined frames 0.84 ms tabulated, 0.794 at 2^18 doubles (the
     // tabulated segments' length), 1.12 at 2^19 (longer generator chains); profiles/r05_pipe_split_ab.txt
     int64_t mt_pipe_split = (int64_t)1 << 18;
-    double* mt_out = nullptr;  // staging for srt_mt19937_uniforms into host memory
-    int64_t mt_out_cap = 0;
+    DevBuf<double> mt_out;  // staging for srt_mt19937_uniforms into host memory
     // -1 auto: k_frame for scenes whose rays branch (refractive / thin-film / diffuse fan-out),
     // per-depth wavefront kernels otherwise.  Measured (one MI355X, Mrays/s, wavefront vs frame):
     // ex1 1080p d5 13388 vs 10478, ex3 1080p d8 8950 vs 9585, ex4 4K d6 14081 vs 17494,
@@ -1768,7 +1826,7 @@ struct srt_ctx {
     // of a lean k_primary, else MT_GEN_THREADS; option "mt_gen_nt" (0 auto, 256 or 320) forces one
     int gen_nt = rtmt_dev::MT_GEN_THREADS;
     int mt_gen_nt_opt = 0;
-    double* red = nullptr;      // srt_comm_allreduce scratch
+    DevBuf<double> red;         // srt_comm_allreduce scratch
     // srt_render_prefetch: the numpy-stream generation of the synchronous whole frame srt_render is
     // about to be called for, queued before the caller lowers and uploads its scene (Scene.render);
     // the next srt_render with the same stream state and frame shape finds it queued and skips its
@@ -1783,29 +1841,22 @@ struct srt_ctx {
         hipStream_t gen_on = nullptr;
     } pf;
     int64_t pf_used = 0, pf_queued = 0;  // (srt_debug_prefetch_counts)
-    unsigned long long* lane_stats = nullptr;  // (srt_debug_lane_stats) [SRT_MAX_DEPTHS][2] or null
+    DevBuf<unsigned long long> lane_stats;  // (srt_debug_lane_stats) [SRT_MAX_DEPTHS][2] or null
+    // streams, events and the communicator (after the frames in flight; the context's device is
+    // current); the members above then release the device memory
+    ~srt_ctx();
 };
 
 namespace {
 
-void free_list(std::vector<void*>& v) {
-    for (void* p : v)
-        if (p) (void)hipFree(p);
-    v.clear();
-}
-
 // the twelve arrays of a ray queue, `n` rays each (recorded in `bufs`)
-int alloc_queue(Queue& q, int64_t n, std::vector<void*>& bufs, const char* what) {
+int alloc_queue(Queue& q, int64_t n, DevList& bufs, const char* what) {
     double** dptr[9] = {&q.ox, &q.oy, &q.oz, &q.dx, &q.dy, &q.dz, &q.wr, &q.wg, &q.wb};
-    for (double** p : dptr) {
-        if (dalloc(p, n) != hipSuccess) return fail(SRT_ERR_MEMORY, what);
-        bufs.push_back(*p);
-    }
+    for (double** p : dptr)
+        if (bufs.alloc(p, n) != hipSuccess) return fail(SRT_ERR_MEMORY, what);
     uint32_t** uptr[3] = {&q.pix, &q.meta, &q.path};
-    for (uint32_t** p : uptr) {
-        if (dalloc(p, n) != hipSuccess) return fail(SRT_ERR_MEMORY, what);
-        bufs.push_back(*p);
-    }
+    for (uint32_t** p : uptr)
+        if (bufs.alloc(p, n) != hipSuccess) return fail(SRT_ERR_MEMORY, what);
     return SRT_OK;
 }
 
@@ -1819,7 +1870,7 @@ int64_t queue_seg_for(int64_t rays) {
 int ensure_queues(FrameSlot& f, int64_t rays) {
     const int64_t seg = queue_seg_for(rays);
     if (seg <= f.seg) return SRT_OK;
-    free_list(f.queue_bufs);
+    f.queue_bufs.clear();
     f.seg = 0;
     for (Queue& q : f.q)
         if (int rc = alloc_queue(q, seg * NSHARD, f.queue_bufs, "ray queue allocation failed")) return rc;
@@ -1840,12 +1891,11 @@ int ensure_ring(srt_ctx* c, FrameSlot& f, int64_t cap) {
     cap = ring_cap_for(cap);
     const int nslot = ring_slots(c);
     if (cap <= f.ring_cap && nslot <= f.nslot) return SRT_OK;
-    free_list(f.ring_bufs);
+    f.ring_bufs.clear();
     f.ring_cap = 0;
     f.nslot = 0;
     if (int rc = alloc_queue(f.ring, cap * nslot, f.ring_bufs, "ray ring allocation failed")) return rc;
-    if (dalloc(&f.ring_lock, nslot) != hipSuccess) return fail(SRT_ERR_MEMORY, "ring lock allocation failed");
-    f.ring_bufs.push_back(f.ring_lock);
+    if (f.ring_bufs.alloc(&f.ring_lock, nslot) != hipSuccess) return fail(SRT_ERR_MEMORY, "ring lock allocation failed");
     HIP_TRY(hipMemset(f.ring_lock, 0, (size_t)nslot * 4));
     f.ring_cap = cap;
     f.nslot = nslot;
@@ -1853,44 +1903,10 @@ int ensure_ring(srt_ctx* c, FrameSlot& f, int64_t cap) {
 }
 
 template <typename T>
-int ensure_buf(T** p, int64_t& cap, int64_t count) {
-    if (count <= cap && *p) return SRT_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    cap = 0;
-    if (dalloc(p, count) != hipSuccess) return fail(SRT_ERR_MEMORY, "device allocation failed");
-    cap = count;
-    return SRT_OK;
-}
-
-// The segment-window table of a slot's numpy-stream generation: zero when (re)allocated; from then
-// on every window a jump XORs into is zeroed again by the generator that reads it.  After a
-// generation that stopped between its jump and generator launches (srt_ctx::mt_dirty) every slot's
-// table and the end accumulator are cleared first (device-synchronous: an error path only).
-int mt_end_reset(srt_ctx* c);
-int mt_win_ensure(srt_ctx* c, FrameSlot& f, int64_t count) {
-    if (c->mt_dirty) {
-        HIP_TRY(hipDeviceSynchronize());
-        for (FrameSlot& s : c->slots)
-            if (s.mt_win) HIP_TRY(hipMemset(s.mt_win, 0, (size_t)s.mt_win_cap * 4));
-        int rc = mt_end_reset(c);
-        if (rc) return rc;
-        c->mt_dirty = false;
-    }
-    if (count <= f.mt_win_cap && f.mt_win) return SRT_OK;
-    int rc = ensure_buf(&f.mt_win, f.mt_win_cap, count);
-    if (rc) return rc;
-    HIP_TRY(hipMemset(f.mt_win, 0, (size_t)count * 4));
-    return SRT_OK;
-}
-
-template <typename T>
 int upload(srt_ctx* c, const T* src, int64_t count, T** dst) {
     *dst = nullptr;
     if (count <= 0 || !src) return SRT_OK;
-    HIP_TRY(dalloc(dst, count));
-    c->scene_bufs.push_back(*dst);
-    HIP_TRY(hipMemcpy(*dst, src, (size_t)count * sizeof(T), hipMemcpyDefault));
+    HIP_TRY(c->scene_bufs.in(dst, src, count));
     return SRT_OK;
 }
 
@@ -1988,25 +2004,6 @@ size_t lut_bytes(const srt_ctx* c) { return (size_t)c->S.nlut_lds * 256 * sizeof
 
 int trace_grid(const srt_ctx* c) { return std::max(NSHARD, (c->max_blocks / NSHARD) * NSHARD); }
 
-int wait_frames(srt_ctx* c, srt_stats* st);
-
-// copy `bytes` from host `src` to device `dst` (on `st`) unless `shadow` (the host copy of what dst
-// holds) already equals it.  The shadow is invalidated whenever the buffer is reallocated (ensure_buf).
-// The camera tables are shared by the frame slots: the frames in flight are waited for before a change.
-int upload_if_changed(srt_ctx* c, hipStream_t st, void* dst, std::vector<uint8_t>& shadow, const void* src,
-                      size_t bytes) {
-    const bool dev = is_device_ptr(src);
-    if (!dev && shadow.size() == bytes && !memcmp(shadow.data(), src, bytes)) return SRT_OK;
-    int rc = c->async_pending > 0 ? wait_frames(c, nullptr) : SRT_OK;
-    if (rc) return rc;
-    if (dev)
-        shadow.clear();
-    else
-        shadow.assign((const uint8_t*)src, (const uint8_t*)src + bytes);
-    HIP_TRY(hipMemcpyAsync(dst, src, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-    return SRT_OK;
-}
-
 int64_t depth_total(const uint32_t* cnt, int64_t seg) {
     int64_t t = 0;
     for (int s = 0; s < NSHARD; ++s) t += std::min<int64_t>(cnt[s], seg);
@@ -2045,12 +2042,30 @@ int mt_end_reset(srt_ctx* c) {
     return SRT_OK;
 }
 
+// The segment-window table of a slot's numpy-stream generation: zero when (re)allocated; from then
+// on every window a jump XORs into is zeroed again by the generator that reads it.  After a
+// generation that stopped between its jump and generator launches (srt_ctx::mt_dirty) every slot's
+// table and the end accumulator are cleared first (device-synchronous: an error path only).
+int mt_win_ensure(srt_ctx* c, FrameSlot& f, int64_t count) {
+    if (c->mt_dirty) {
+        HIP_TRY(hipDeviceSynchronize());
+        for (FrameSlot& s : c->slots)
+            if (s.mt_win) HIP_TRY(hipMemset(s.mt_win, 0, (size_t)s.mt_win.cap * 4));
+        int rc = mt_end_reset(c);
+        if (rc) return rc;
+        c->mt_dirty = false;
+    }
+    if (count <= f.mt_win.cap && f.mt_win) return SRT_OK;
+    int rc = f.mt_win.ensure(count);
+    if (rc) return rc;
+    HIP_TRY(hipMemset(f.mt_win, 0, (size_t)count * 4));
+    return SRT_OK;
+}
+
 // Blocks per jump window (k_mt_jump parts): the option, else 4 (final build, same box, against 8:
 // device-side whole frame 0.988 -> 0.979 ms, a rank of 8 0.204 -> 0.202, of 4 0.328 -> 0.318;
 // profiles/r04_jump_parts_ab.txt)
 int mt_jump_parts(const srt_ctx* c) { return c->mt_parts_opt ? c->mt_parts_opt : 4; }
-
-
 
 // The y words of `key` for a generation on `st`: those an end block made with the key (a final
 // window), else k_mt_y into the scratch buffer (one workgroup, ~34 blocks).  Generations of
@@ -2066,12 +2081,12 @@ const uint32_t* mt_y_for(srt_ctx* c, hipStream_t st, const uint32_t* key) {
 int mt_end_poly_for(srt_ctx* c, int64_t n_words, const uint32_t** out) {
     for (auto& e : c->mt_end_polys)
         if (e.first == n_words) { *out = e.second; return SRT_OK; }
-    uint32_t* d = nullptr;
+    DevBuf<uint32_t> d;
     HIP_TRY(dalloc(&d, rtmt::N));
     const std::vector<uint32_t> poly = rtmt::xpow_mod(rtmt::end_jump(n_words));
     HIP_TRY(hipMemcpy(d, poly.data(), rtmt::N * 4, hipMemcpyHostToDevice));
-    c->mt_end_polys.emplace_back(n_words, d);
     *out = d;
+    c->mt_end_polys.emplace_back(n_words, std::move(d));
     return SRT_OK;
 }
 
@@ -2175,7 +2190,7 @@ int mt_band_table(srt_ctx* c, int64_t W, int64_t Hf, int ns, int plane_mask, con
     HIP_TRY(dalloc(&T.polys, (int64_t)polys.size()));
     HIP_TRY(hipMemcpy(T.bands, segs.data(), segs.size() * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(T.polys, polys.data(), polys.size() * 4, hipMemcpyHostToDevice));
-    c->mt_bandtabs.push_back(T);
+    c->mt_bandtabs.push_back(std::move(T));
     *out = &c->mt_bandtabs.back();
     return SRT_OK;
 }
@@ -2398,19 +2413,16 @@ int ensure_slot(FrameSlot& f) {
 void free_slot(FrameSlot& f) {
     if (!f.stream) return;
     (void)hipStreamSynchronize(f.stream);
-    free_list(f.queue_bufs);
-    free_list(f.ring_bufs);
-    void* bufs[] = {f.fb, f.fbg, f.fbx, f.rgb, f.u8, f.jit, f.hit, f.counts, f.flags, f.shadow, f.g_u8, f.g_rgb, f.full_u8, f.full_rgb,
-                    f.mt_win};
-    for (void* p : bufs)
-        if (p) (void)hipFree(p);
-    for (hipEvent_t e : f.ev) (void)hipEventDestroy(e);
-    if (f.host) (void)hipHostFree(f.host);
-    (void)hipEventDestroy(f.jit_ready);
-    (void)hipEventDestroy(f.jit_free);
-    (void)hipEventDestroy(f.mt_jumped);
-    (void)hipStreamDestroy(f.stream);
+    // the device memory first (its owners release it), then the events, the pinned memory and the stream
+    const std::vector<hipEvent_t> ev = f.ev;
+    const hipEvent_t own[3] = {f.jit_ready, f.jit_free, f.mt_jumped};
+    uint32_t* const host = f.host;
+    const hipStream_t stream = f.stream;
     f = FrameSlot{};
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    if (host) (void)hipHostFree(host);
+    for (hipEvent_t e : own) (void)hipEventDestroy(e);
+    (void)hipStreamDestroy(stream);
 }
 
 // Wait for the asynchronous frames in flight and check them (flags accumulated over all of them,
@@ -2471,6 +2483,23 @@ int finish_async(srt_ctx* c, srt_stats* st) {
     return rc;
 }
 
+// copy `bytes` from host `src` to device `dst` (on `st`) unless `shadow` (the host copy of what dst
+// holds) already equals it.  The shadow is invalidated whenever the buffer is reallocated (DevBuf::ensure).
+// The camera tables are shared by the frame slots: the frames in flight are waited for before a change.
+int upload_if_changed(srt_ctx* c, hipStream_t st, void* dst, std::vector<uint8_t>& shadow, const void* src,
+                      size_t bytes) {
+    const bool dev = is_device_ptr(src);
+    if (!dev && shadow.size() == bytes && !memcmp(shadow.data(), src, bytes)) return SRT_OK;
+    int rc = c->async_pending > 0 ? wait_frames(c, nullptr) : SRT_OK;
+    if (rc) return rc;
+    if (dev)
+        shadow.clear();
+    else
+        shadow.assign((const uint8_t*)src, (const uint8_t*)src + bytes);
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    return SRT_OK;
+}
+
 int64_t shard_npix(const FrameSlot::Gather& G, int nranks, int q) {
     return shard_rank_rows(G.H, nranks, q, G.band) * G.W;
 }
@@ -2495,19 +2524,6 @@ int gather_post(srt_ctx* c) {
     return SRT_OK;
 }
 
-int gather_finish(srt_ctx* c);
-
-// The frame's gather on its own (one rank per process): post it in a group, assemble on rank 0.
-int gather_frame(srt_ctx* c) {
-    if (c->nranks > 1) {
-        NCCL_TRY(ncclGroupStart());
-        int rc = gather_post(c);
-        NCCL_TRY(ncclGroupEnd());
-        if (rc) return rc;
-    }
-    return gather_finish(c);
-}
-
 // Rank 0, after the gather: the tiles into the frame, then to the caller's host buffers if any.
 int gather_finish(srt_ctx* c) {
     const FrameSlot::Gather& G = c->f->gather;
@@ -2528,7 +2544,26 @@ int gather_finish(srt_ctx* c) {
     return SRT_OK;
 }
 
+// The frame's gather on its own (one rank per process): post it in a group, assemble on rank 0.
+int gather_frame(srt_ctx* c) {
+    if (c->nranks > 1) {
+        NCCL_TRY(ncclGroupStart());
+        int rc = gather_post(c);
+        NCCL_TRY(ncclGroupEnd());
+        if (rc) return rc;
+    }
+    return gather_finish(c);
+}
+
 }  // namespace
+
+srt_ctx::~srt_ctx() {
+    for (FrameSlot& s : slots) free_slot(s);
+    scene_bufs.clear();
+    if (comm) (void)ncclCommDestroy(comm);
+    if (mt_done) (void)hipEventDestroy(mt_done);
+    if (mt_stream) (void)hipStreamDestroy(mt_stream);
+}
 
 extern "C" {
 
@@ -2585,20 +2620,7 @@ int srt_destroy(srt_ctx* c) {
     if (!c) return SRT_OK;
     (void)hipSetDevice(c->device);
     (void)finish_async(c, nullptr);
-    for (FrameSlot& f : c->slots) free_slot(f);
-    free_list(c->scene_bufs);
-    if (c->comm) (void)ncclCommDestroy(c->comm);
-    if (c->mt_done) (void)hipEventDestroy(c->mt_done);
-    if (c->mt_stream) (void)hipStreamDestroy(c->mt_stream);
-    void* bufs[] = {c->xs, c->ys, c->rows, c->mt, c->mt_out, c->texels, c->red, c->mt_y, c->lane_stats};
-    for (void* p : bufs)
-        if (p) (void)hipFree(p);
-    for (auto& t : c->mt_bandtabs) {
-        (void)hipFree(t.bands);
-        (void)hipFree(t.polys);
-    }
-    for (auto& e : c->mt_end_polys) (void)hipFree(e.second);
-    delete c;
+    delete c;  // (~srt_ctx, then the members that own device memory)
     return SRT_OK;
 }
 
@@ -2669,8 +2691,9 @@ int srt_set_option(srt_ctx* c, const char* key, int64_t value) {
     return fail(SRT_ERR_ARG, std::string("unknown option ") + key);
 }
 
-int srt_upload_scene(srt_ctx* c, const srt_scene_desc* d) {
-    if (!c || !d) return fail(SRT_ERR_ARG, "null ctx/scene");
+// ---- srt_upload_scene, step by step ----
+// 1. the descriptor's own consistency (no HIP call)
+static int check_scene_desc(const srt_scene_desc* d) {
     if (d->n_colliders < 0 || d->n_materials < 0 || d->n_media < 1 || d->n_media > 255)
         return fail(SRT_ERR_ARG, "scene needs 1 <= n_media <= 255 (row 0 = scene.n)");
     for (int i = 0; i < d->n_colliders; ++i) {
@@ -2708,29 +2731,27 @@ int srt_upload_scene(srt_ctx* c, const srt_scene_desc* d) {
     for (int i = 0; i < d->n_lights; ++i)
         if (d->lights[i].type < SRT_LIGHT_DIRECTIONAL || d->lights[i].type > SRT_LIGHT_USER)
             return fail(SRT_ERR_ARG, "bad light type");
-    HIP_TRY(hipSetDevice(c->device));
-    int rc0 = finish_async(c, nullptr);  // frames in flight read the scene tables freed below
-    if (rc0) return rc0;
-    HIP_TRY(hipStreamSynchronize(c->f->stream));
-    free_list(c->scene_bufs);
-    c->has_scene = false;
-    SceneView S{};
-    int rc;
-    srt_collider* col;
-    srt_material* mat;
-    srt_texture* tex;
-    uint8_t* texels;
-    srt_light* lights;
-    double *media, *f0, *ll, *imp;
-    if ((rc = upload(c, d->colliders, d->n_colliders, &col))) return rc;
-    if ((rc = upload(c, d->materials, d->n_materials, &mat))) return rc;
-    // texel pool in HBM: 3-channel images as 4-byte texels (RGBX), so that a texel is one aligned
-    // dword load (texel_rgb) instead of three byte loads; the records point into that layout
-    std::vector<srt_texture> tex_h(d->textures, d->textures + std::max(0, d->n_textures));
+    return SRT_OK;
+}
+
+// 2. the texel pool in HBM: 3-channel images as 4-byte texels (RGBX), so that a texel is one aligned
+// dword load (texel_rgb) instead of three byte loads; the records point into that layout
+struct TexelPool {
+    std::vector<srt_texture> tex;              // the texture records, their offsets in the pool's layout
     std::vector<std::array<int64_t, 4>> imgs;  // (offset, bytes, new offset, expand) per image
-    bool rgbx = d->texel_bytes > 0 && d->texels && !is_device_ptr(d->texels);
+    bool rgbx = false;                         // repacked (else the caller's pool as given)
+    int64_t bytes = 0;
+    uint64_t layout = 0;  // hash of the layout
+};
+
+// the pool's layout (no HIP call); `host_texels`: the caller's texels can be repacked on the host
+static TexelPool plan_texel_pool(const srt_scene_desc* d, bool host_texels) {
+    TexelPool tp;
+    tp.tex.assign(d->textures, d->textures + std::max(0, d->n_textures));
+    auto& imgs = tp.imgs;
+    bool rgbx = host_texels;
     if (rgbx) {
-        for (const srt_texture& t : tex_h) {
+        for (const srt_texture& t : tp.tex) {
             const int64_t bytes = (int64_t)t.height * t.width * t.channels;
             bool seen = false;
             for (auto& im : imgs)
@@ -2743,64 +2764,86 @@ int srt_upload_scene(srt_ctx* c, const srt_scene_desc* d) {
         std::sort(imgs.begin(), imgs.end());
         for (size_t k = 1; k < imgs.size(); ++k) rgbx = rgbx && imgs[k][0] >= imgs[k - 1][0] + imgs[k - 1][1];
     }
-    int64_t pool_bytes = d->texel_bytes;
+    tp.bytes = d->texel_bytes;
     if (rgbx) {
-        pool_bytes = 0;
+        tp.bytes = 0;
         for (auto& im : imgs) {
-            im[2] = pool_bytes;
-            pool_bytes += ((im[3] ? im[1] / 3 * 4 : im[1]) + 3) / 4 * 4;
+            im[2] = tp.bytes;
+            tp.bytes += ((im[3] ? im[1] / 3 * 4 : im[1]) + 3) / 4 * 4;
         }
-        for (srt_texture& t : tex_h)
+        for (srt_texture& t : tp.tex)
             for (auto& im : imgs)
                 if (im[0] == t.offset) {
                     t.offset = im[2];
                     if (im[3]) t.channels = 4;
                 }
     }
-    if ((rc = upload(c, tex_h.data(), d->n_textures, &tex))) return rc;
+    tp.rgbx = rgbx;
     // the pool's layout: the images (caller offset, bytes, pool offset, expanded) it holds, or the
     // caller's pool as given -- a key reused with another image set must not reuse the pool
     uint64_t layout = 1469598103934665603ull;
     auto mix = [&layout](int64_t v) { layout = (layout ^ (uint64_t)v) * 1099511628211ull; };
-    mix(pool_bytes);
+    mix(tp.bytes);
     mix(rgbx);
     if (rgbx)
         for (const auto& im : imgs)
             for (int64_t v : im) mix(v);
-    // kept in HBM across uploads while the caller's key and size and the layout are unchanged
-    if (d->texel_key != 0 && d->texel_key == c->texel_key && d->texel_bytes == c->texel_bytes && c->texels &&
-        rgbx == c->texels_rgbx && layout == c->texel_layout) {
-        texels = c->texels;
-    } else {
-        if (c->texels) (void)hipFree(c->texels);
-        c->texels = nullptr;
-        c->texel_key = 0;
-        c->texel_bytes = 0;
-        texels = nullptr;
-        if (d->texel_bytes > 0 && d->texels) {
-            HIP_TRY(dalloc(&texels, pool_bytes));
-            if (rgbx) {
-                std::vector<uint8_t> h((size_t)pool_bytes, 0);
-                for (const auto& im : imgs) {
-                    const uint8_t* src = d->texels + im[0];
-                    uint8_t* dst = h.data() + im[2];
-                    if (im[3]) {
-                        for (int64_t i = 0, n = im[1] / 3; i < n; ++i) memcpy(dst + 4 * i, src + 3 * i, 3);
-                    } else {
-                        memcpy(dst, src, (size_t)im[1]);
-                    }
-                }
-                HIP_TRY(hipMemcpy(texels, h.data(), (size_t)pool_bytes, hipMemcpyHostToDevice));
-            } else {
-                HIP_TRY(hipMemcpy(texels, d->texels, (size_t)d->texel_bytes, hipMemcpyDefault));
-            }
-            c->texels = texels;
-            c->texel_key = d->texel_key;
-            c->texel_bytes = d->texel_bytes;
-            c->texels_rgbx = rgbx;
-            c->texel_layout = layout;
+    tp.layout = layout;
+    return tp;
+}
+
+// the caller's texels in the planned layout (host memory)
+static std::vector<uint8_t> pack_texel_pool(const srt_scene_desc* d, const TexelPool& tp) {
+    std::vector<uint8_t> h((size_t)tp.bytes, 0);
+    for (const auto& im : tp.imgs) {
+        const uint8_t* src = d->texels + im[0];
+        uint8_t* dst = h.data() + im[2];
+        if (im[3]) {
+            for (int64_t i = 0, n = im[1] / 3; i < n; ++i) memcpy(dst + 4 * i, src + 3 * i, 3);
+        } else {
+            memcpy(dst, src, (size_t)im[1]);
         }
     }
+    return h;
+}
+
+// the pool on the device: kept in HBM across uploads while the caller's key and size and the layout
+// are unchanged (it is no scene buffer), else packed and copied
+static int upload_texel_pool(srt_ctx* c, const srt_scene_desc* d, const TexelPool& tp) {
+    if (d->texel_key != 0 && d->texel_key == c->texel_key && d->texel_bytes == c->texel_bytes && c->texels &&
+        tp.rgbx == c->texels_rgbx && tp.layout == c->texel_layout)
+        return SRT_OK;
+    (void)c->texels.reset();
+    c->texel_key = 0;
+    c->texel_bytes = 0;
+    if (d->texel_bytes <= 0 || !d->texels) return SRT_OK;
+    HIP_TRY(dalloc(&c->texels, tp.bytes));
+    if (tp.rgbx)
+        HIP_TRY(hipMemcpy(c->texels, pack_texel_pool(d, tp).data(), (size_t)tp.bytes, hipMemcpyHostToDevice));
+    else
+        HIP_TRY(hipMemcpy(c->texels, d->texels, (size_t)d->texel_bytes, hipMemcpyDefault));
+    c->texel_key = d->texel_key;
+    c->texel_bytes = d->texel_bytes;
+    c->texels_rgbx = tp.rgbx;
+    c->texel_layout = tp.layout;
+    return SRT_OK;
+}
+
+// 3. the scene's tables and the BVH over its Triangle colliders into scene_bufs, the texel pool (step 2)
+// planned and uploaded between them; `S` receives the view the kernels read, `lin_tri` whether a
+// Triangle stays outside the BVH
+static int upload_tables(srt_ctx* c, const srt_scene_desc* d, SceneView& S, bool& lin_tri) {
+    int rc;
+    srt_collider* col;
+    srt_material* mat;
+    srt_texture* tex;
+    srt_light* lights;
+    double *media, *f0, *ll, *imp;
+    if ((rc = upload(c, d->colliders, d->n_colliders, &col))) return rc;
+    if ((rc = upload(c, d->materials, d->n_materials, &mat))) return rc;
+    const TexelPool tp = plan_texel_pool(d, d->texel_bytes > 0 && d->texels && !is_device_ptr(d->texels));
+    if ((rc = upload(c, tp.tex.data(), d->n_textures, &tex))) return rc;
+    if ((rc = upload_texel_pool(c, d, tp))) return rc;
     if ((rc = upload(c, d->lights, d->n_lights, &lights))) return rc;
     if ((rc = upload(c, d->media, (int64_t)d->n_media * 6, &media))) return rc;
     if ((rc = upload(c, d->glossy_f0, (int64_t)d->n_materials * d->n_media * 3, &f0))) return rc;
@@ -2808,48 +2851,51 @@ int srt_upload_scene(srt_ctx* c, const srt_scene_desc* d) {
     if ((rc = upload(c, d->importance, (int64_t)d->n_importance * 4, &imp))) return rc;
     // (casts: in the device compilation the SceneView fields are constant-address-space pointers)
     S.col = (decltype(S.col))col; S.mat = (decltype(S.mat))mat; S.tex = (decltype(S.tex))tex;
-    S.texels = (decltype(S.texels))texels; S.lights = (decltype(S.lights))lights;
+    S.texels = (decltype(S.texels))c->texels.p; S.lights = (decltype(S.lights))lights;
     S.media = (decltype(S.media))media; S.glossy_f0 = (decltype(S.glossy_f0))f0;
     S.light_local = (decltype(S.light_local))ll; S.importance = (decltype(S.importance))imp;
     S.ncol = d->n_colliders; S.nmat = d->n_materials; S.ntex = d->n_textures; S.nlights = d->n_lights;
     S.nmedia = d->n_media; S.nimp = d->n_importance;
     S.sky_col = sky_collider(d->colliders, d->n_colliders, d->materials);
-    S.nshadow = 0;
-    bool lin_tri = false;
-    {
-        // triangle meshes: BVH over the Triangle colliders, the rest intersected one by one
-        BvhBuild B;
-        lin_tri = false;
-        if (c->use_bvh) {
-            bvh_build(d->colliders, d->n_colliders, B);
-        } else {
-            for (int i = 0; i < d->n_colliders; ++i) B.lin.push_back(i);
-        }
-        int32_t *lin, *tri;
-        BvhNode* nodes;
-        if ((rc = upload(c, B.lin.data(), (int64_t)B.lin.size(), &lin))) return rc;
-        if ((rc = upload(c, B.tri.data(), (int64_t)B.tri.size(), &tri))) return rc;
-        if ((rc = upload(c, B.nodes.data(), (int64_t)B.nodes.size(), &nodes))) return rc;
-        S.nlin = (int)B.lin.size();
-        S.lin = (decltype(S.lin))lin;
-        S.bvh_tri = (decltype(S.bvh_tri))tri;
-        S.bvh = (decltype(S.bvh))nodes;
-        S.bvh_nodes = (int)B.nodes.size();
-        S.bvh_bound = B.bound;
-        for (int k : B.lin) lin_tri |= d->colliders[k].type == SRT_TRIANGLE;
+    // triangle meshes: BVH over the Triangle colliders, the rest intersected one by one
+    BvhBuild B;
+    if (c->use_bvh) {
+        bvh_build(d->colliders, d->n_colliders, B);
+    } else {
+        for (int i = 0; i < d->n_colliders; ++i) B.lin.push_back(i);
     }
-    int fan = 1;
-    c->has_diffuse = 0;
+    int32_t *lin, *tri;
+    BvhNode* nodes;
+    if ((rc = upload(c, B.lin.data(), (int64_t)B.lin.size(), &lin))) return rc;
+    if ((rc = upload(c, B.tri.data(), (int64_t)B.tri.size(), &tri))) return rc;
+    if ((rc = upload(c, B.nodes.data(), (int64_t)B.nodes.size(), &nodes))) return rc;
+    S.nlin = (int)B.lin.size();
+    S.lin = (decltype(S.lin))lin;
+    S.bvh_tri = (decltype(S.bvh_tri))tri;
+    S.bvh = (decltype(S.bvh))nodes;
+    S.bvh_nodes = (int)B.nodes.size();
+    S.bvh_bound = B.bound;
+    lin_tri = false;
+    for (int k : B.lin) lin_tri |= d->colliders[k].type == SRT_TRIANGLE;
+    S.nshadow = 0;
     for (int i = 0; i < d->n_colliders; ++i)
         if (d->colliders[i].flags & SRT_CF_SHADOW) S.nshadow++;
+    for (int k = 0; k < 3; ++k) S.ambient[k] = d->ambient[k];
+    S.lut_lds = nullptr;
+    S.nlut_lds = std::min(d->n_textures, MAX_LUT_LDS);
+    return SRT_OK;
+}
+
+// 4. what the context keeps of the scene besides its view: depth and fan-out, the materials present
+// (the kernel variant), the collider sequence, who needs per-hit inputs
+static void derive_scene_facts(srt_ctx* c, const srt_scene_desc* d, const SceneView& S, bool lin_tri) {
+    int fan = 1;
+    c->has_diffuse = 0;
     for (int i = 0; i < d->n_materials; ++i) {
         const srt_material& m = d->materials[i];
         if (m.type == SRT_REFRACTIVE || m.type == SRT_THINFILM) fan = std::max(fan, 2);
         if (m.type == SRT_DIFFUSE) { fan = std::max(fan, std::max(1, (int)m.ival)); c->has_diffuse = 1; }
     }
-    for (int k = 0; k < 3; ++k) S.ambient[k] = d->ambient[k];
-    S.lut_lds = nullptr;
-    S.nlut_lds = std::min(d->n_textures, MAX_LUT_LDS);
     c->S = S;
     c->max_depth = std::max(0, (int)d->max_ray_depth);
     c->fanout = fan;
@@ -2877,8 +2923,23 @@ int srt_upload_scene(srt_ctx* c, const srt_scene_desc* d) {
     if (c->n_user_lights > 0) c->needs_inputs = true;
     c->chain_ok = true;
     c->hint_key[0] = -1;  // ray counts of another scene are no plan for this one
-    c->has_scene = true;
     c->fx_ok = true;
+}
+
+int srt_upload_scene(srt_ctx* c, const srt_scene_desc* d) {
+    if (!c || !d) return fail(SRT_ERR_ARG, "null ctx/scene");
+    int rc;
+    if ((rc = check_scene_desc(d))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = finish_async(c, nullptr))) return rc;  // frames in flight read the scene tables freed below
+    HIP_TRY(hipStreamSynchronize(c->f->stream));
+    c->scene_bufs.clear();
+    c->has_scene = false;
+    SceneView S{};
+    bool lin_tri = false;
+    if ((rc = upload_tables(c, d, S, lin_tri))) return rc;
+    derive_scene_facts(c, d, S, lin_tri);
+    c->has_scene = true;
     return SRT_OK;
 }
 
@@ -2930,39 +2991,29 @@ int trace_impl(srt_ctx* c, const srt_trace_args* a, const int32_t* fid, const do
     c->f->dirty = true;  // counts/flags/shadow are left as this call's memsets and kernels leave them
     const int64_t n = a->n;
     int rc = SRT_OK;
-    CallBufs bufs;  // (freed on every return)
+    DevList bufs;  // (freed on every return)
+    const hipStream_t st0 = c->f->stream;
     double *O = nullptr, *D = nullptr;
     int32_t* med = nullptr;
-    HIP_TRY(bufs.alloc(&O, 3 * n));
-    HIP_TRY(bufs.alloc(&D, 3 * n));
-    if (a->medium) HIP_TRY(bufs.alloc(&med, n));
-    HIP_TRY(hipMemcpyAsync(O, a->origin, (size_t)3 * n * 8, hipMemcpyDefault, c->f->stream));
-    HIP_TRY(hipMemcpyAsync(D, a->dir, (size_t)3 * n * 8, hipMemcpyDefault, c->f->stream));
-    if (med) HIP_TRY(hipMemcpyAsync(med, a->medium, (size_t)n * 4, hipMemcpyDefault, c->f->stream));
+    HIP_TRY(bufs.in(&O, a->origin, 3 * n, st0));
+    HIP_TRY(bufs.in(&D, a->dir, 3 * n, st0));
+    if (a->medium) HIP_TRY(bufs.in(&med, a->medium, n, st0));
     // the user's per-hit values, copied in with the other per-call buffers
     double *dalb = nullptr, *dldist = nullptr, *dlirr = nullptr;
-    if (in && in->albedo) {
-        HIP_TRY(bufs.alloc(&dalb, 3 * n));
-        HIP_TRY(hipMemcpyAsync(dalb, in->albedo, (size_t)3 * n * 8, hipMemcpyDefault, c->f->stream));
-    }
+    if (in && in->albedo) HIP_TRY(bufs.in(&dalb, in->albedo, 3 * n, st0));
     if (in && in->n_lights > 0) {
-        HIP_TRY(bufs.alloc(&dldist, (int64_t)in->n_lights * n));
-        HIP_TRY(bufs.alloc(&dlirr, (int64_t)in->n_lights * 3 * n));
-        HIP_TRY(hipMemcpyAsync(dldist, in->light_dist, (size_t)in->n_lights * n * 8, hipMemcpyDefault, c->f->stream));
-        HIP_TRY(hipMemcpyAsync(dlirr, in->light_irr, (size_t)in->n_lights * 3 * n * 8, hipMemcpyDefault, c->f->stream));
+        HIP_TRY(bufs.in(&dldist, in->light_dist, (int64_t)in->n_lights * n, st0));
+        HIP_TRY(bufs.in(&dlirr, in->light_irr, (int64_t)in->n_lights * 3 * n, st0));
     }
     int32_t* dfid = nullptr;
     double *dft = nullptr, *dfo = nullptr;
     if (fid) {
-        HIP_TRY(bufs.alloc(&dfid, n));
-        HIP_TRY(bufs.alloc(&dft, n));
-        HIP_TRY(bufs.alloc(&dfo, n));
-        HIP_TRY(hipMemcpyAsync(dfid, fid, (size_t)n * 4, hipMemcpyDefault, c->f->stream));
-        HIP_TRY(hipMemcpyAsync(dft, ft, (size_t)n * 8, hipMemcpyDefault, c->f->stream));
-        HIP_TRY(hipMemcpyAsync(dfo, fo, (size_t)n * 8, hipMemcpyDefault, c->f->stream));
+        HIP_TRY(bufs.in(&dfid, fid, n, st0));
+        HIP_TRY(bufs.in(&dft, ft, n, st0));
+        HIP_TRY(bufs.in(&dfo, fo, n, st0));
     }
-    if ((rc = ensure_buf(&c->f->fb, c->f->fb_cap, 3 * n))) return rc;
-    if ((rc = ensure_buf(&c->f->fbx, c->f->fbx_cap, fx_words(n)))) return rc;
+    if ((rc = c->f->fb.ensure(3 * n))) return rc;
+    if ((rc = c->f->fbx.ensure(fx_words(n)))) return rc;
     if ((rc = ensure_queues(*c->f, n * c->fanout))) return rc;
     // depths a->depth .. a->depth + cap (the batch's depth is a scalar in the reference)
     const int d0 = a->depth;
@@ -3048,7 +3099,7 @@ int trace_impl(srt_ctx* c, const srt_trace_args* a, const int32_t* fid, const do
                 continue;
             }
         }
-        HIP_TRY(hipMemcpyAsync(a->out_rgb, c->f->fb, (size_t)3 * n * 8, hipMemcpyDefault, c->f->stream));
+        HIP_TRY(bufs.copy(a->out_rgb, c->f->fb.p, 3 * n, st0));
         HIP_TRY(hipStreamSynchronize(c->f->stream));
         if (kids) {
             // the first depth's children, packed shard by shard (the order the queue appends gave them)
@@ -3082,18 +3133,14 @@ int trace_impl(srt_ctx* c, const srt_trace_args* a, const int32_t* fid, const do
                                    kd, kf);
                 HIP_TRY(hipGetLastError());
                 for (int k = 0; k < 3; ++k) {
-                    HIP_TRY(hipMemcpyAsync(kids->origin + k * kids->cap, kO + k * total, (size_t)total * 8,
-                                           hipMemcpyDefault, c->f->stream));
-                    HIP_TRY(hipMemcpyAsync(kids->dir + k * kids->cap, kD + k * total, (size_t)total * 8,
-                                           hipMemcpyDefault, c->f->stream));
-                    HIP_TRY(hipMemcpyAsync(kids->weight + k * kids->cap, kW + k * total, (size_t)total * 8,
-                                           hipMemcpyDefault, c->f->stream));
+                    HIP_TRY(bufs.copy(kids->origin + k * kids->cap, kO + k * total, total, st0));
+                    HIP_TRY(bufs.copy(kids->dir + k * kids->cap, kD + k * total, total, st0));
+                    HIP_TRY(bufs.copy(kids->weight + k * kids->cap, kW + k * total, total, st0));
                 }
-                HIP_TRY(hipMemcpyAsync(kids->parent, kp, (size_t)total * 4, hipMemcpyDefault, c->f->stream));
-                HIP_TRY(hipMemcpyAsync(kids->medium, km, (size_t)total * 4, hipMemcpyDefault, c->f->stream));
-                HIP_TRY(hipMemcpyAsync(kids->depth, kd, (size_t)total * 4, hipMemcpyDefault, c->f->stream));
-                HIP_TRY(hipMemcpyAsync(kids->diffuse_reflections, kf, (size_t)total * 4, hipMemcpyDefault,
-                                       c->f->stream));
+                HIP_TRY(bufs.copy(kids->parent, kp, total, st0));
+                HIP_TRY(bufs.copy(kids->medium, km, total, st0));
+                HIP_TRY(bufs.copy(kids->depth, kd, total, st0));
+                HIP_TRY(bufs.copy(kids->diffuse_reflections, kf, total, st0));
                 HIP_TRY(hipStreamSynchronize(c->f->stream));
             }
         }
@@ -3102,6 +3149,31 @@ int trace_impl(srt_ctx* c, const srt_trace_args* a, const int32_t* fid, const do
     if (rc) return rc;
     S.ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     if (st) *st = S;
+    return SRT_OK;
+}
+
+// the hit and children arrays of the shade-level entry points (the children's count starts at zero)
+int check_level_args(const int32_t* collider, const double* t, const double* orient, srt_children* kids) {
+    if (!collider || !t || !orient || !kids) return fail(SRT_ERR_ARG, "null hit / children arrays");
+    kids->n = 0;
+    if (kids->cap < 0 || (kids->cap > 0 && (!kids->origin || !kids->dir || !kids->weight || !kids->parent ||
+                                            !kids->medium || !kids->depth || !kids->diffuse_reflections)))
+        return fail(SRT_ERR_ARG, "srt_children arrays");
+    return SRT_OK;
+}
+
+// The shared tail of the single-kernel entry points: `kernel` over `n` items on the current slot's
+// stream, checked and waited for.  With `dflags` the kernel's flag word is read back and judged
+// (check_flags) into *flag_rc, which the entry point returns once its outputs are copied.
+template <typename K, typename... A>
+int run_kernel(srt_ctx* c, int64_t n, const uint32_t* dflags, int* flag_rc, K kernel, A... args) {
+    hipLaunchKernelGGL(kernel, dim3(grid_for(n, c->max_blocks)), dim3(BLOCK), 0, c->f->stream, args...);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->f->stream));
+    if (!dflags) return SRT_OK;
+    uint32_t flags = 0;
+    HIP_TRY(hipMemcpy(&flags, dflags, 4, hipMemcpyDefault));
+    *flag_rc = check_flags(flags);
     return SRT_OK;
 }
 }  // namespace
@@ -3120,11 +3192,7 @@ int srt_shade(srt_ctx* c, const srt_trace_args* a, const int32_t* collider, cons
 
 int srt_shade_level(srt_ctx* c, const srt_trace_args* a, const int32_t* collider, const double* t, const double* orient,
                     srt_children* kids, srt_stats* st) {
-    if (!collider || !t || !orient || !kids) return fail(SRT_ERR_ARG, "null hit / children arrays");
-    kids->n = 0;
-    if (kids->cap < 0 || (kids->cap > 0 && (!kids->origin || !kids->dir || !kids->weight || !kids->parent ||
-                                            !kids->medium || !kids->depth || !kids->diffuse_reflections)))
-        return fail(SRT_ERR_ARG, "srt_children arrays");
+    if (int rc = check_level_args(collider, t, orient, kids)) return rc;
     return trace_impl(c, a, collider, t, orient, st, kids, nullptr, "srt_shade_level");
 }
 
@@ -3136,11 +3204,7 @@ int srt_shade_level_inputs(srt_ctx* c, const srt_trace_args* a, const int32_t* c
         if (!c || !c->has_scene || !c->needs_inputs) return srt_shade_level(c, a, collider, t, orient, kids, st);
     }
     if (!c || !a) return fail(SRT_ERR_ARG, "null argument");
-    if (!collider || !t || !orient || !kids) return fail(SRT_ERR_ARG, "null hit / children arrays");
-    kids->n = 0;
-    if (kids->cap < 0 || (kids->cap > 0 && (!kids->origin || !kids->dir || !kids->weight || !kids->parent ||
-                                            !kids->medium || !kids->depth || !kids->diffuse_reflections)))
-        return fail(SRT_ERR_ARG, "srt_children arrays");
+    if (int rc = check_level_args(collider, t, orient, kids)) return rc;
     if (!c->has_scene) return fail(SRT_ERR_NOSCENE, "no scene uploaded");
     const srt_hit_inputs none{nullptr, 0, nullptr, nullptr};
     if (!in) in = &none;
@@ -3174,23 +3238,18 @@ int srt_nearest(srt_ctx* c, const double* O, const double* D, int64_t n, double*
     if (!c->has_scene) return fail(SRT_ERR_NOSCENE, "no scene uploaded");
     if (n <= 0) return SRT_OK;
     HIP_TRY(hipSetDevice(c->device));
-    CallBufs bufs;
+    DevList bufs;
     double *dO, *dD, *dt, *dor;
     int32_t* did;
-    HIP_TRY(bufs.alloc(&dO, 3 * n));
-    HIP_TRY(bufs.alloc(&dD, 3 * n));
+    HIP_TRY(bufs.in(&dO, O, 3 * n));
+    HIP_TRY(bufs.in(&dD, D, 3 * n));
     HIP_TRY(bufs.alloc(&dt, n));
     HIP_TRY(bufs.alloc(&dor, n));
     HIP_TRY(bufs.alloc(&did, n));
-    HIP_TRY(hipMemcpy(dO, O, (size_t)3 * n * 8, hipMemcpyDefault));
-    HIP_TRY(hipMemcpy(dD, D, (size_t)3 * n * 8, hipMemcpyDefault));
-    hipLaunchKernelGGL(k_nearest, dim3(grid_for(n, c->max_blocks)), dim3(BLOCK), 0, c->f->stream, c->S, dO, dD, n, dt, did,
-                       dor);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->f->stream));
-    if (t) HIP_TRY(hipMemcpy(t, dt, (size_t)n * 8, hipMemcpyDefault));
-    if (id) HIP_TRY(hipMemcpy(id, did, (size_t)n * 4, hipMemcpyDefault));
-    if (orient) HIP_TRY(hipMemcpy(orient, dor, (size_t)n * 8, hipMemcpyDefault));
+    if (int rc = run_kernel(c, n, nullptr, nullptr, k_nearest, c->S, dO, dD, n, dt, did, dor)) return rc;
+    if (t) HIP_TRY(bufs.copy(t, dt, n));
+    if (id) HIP_TRY(bufs.copy(id, did, n));
+    if (orient) HIP_TRY(bufs.copy(orient, dor, n));
     return SRT_OK;
 }
 
@@ -3200,21 +3259,15 @@ int srt_intersect_collider(srt_ctx* c, const srt_collider* col, const double* O,
     if (col->type < 0 || col->type > 3) return fail(SRT_ERR_ARG, "bad collider type");
     if (n <= 0) return SRT_OK;
     HIP_TRY(hipSetDevice(c->device));
-    CallBufs bufs;
+    DevList bufs;
     double *dO, *dD, *dout;
     srt_collider* dcol;
-    HIP_TRY(bufs.alloc(&dO, 3 * n));
-    HIP_TRY(bufs.alloc(&dD, 3 * n));
+    HIP_TRY(bufs.in(&dO, O, 3 * n));
+    HIP_TRY(bufs.in(&dD, D, 3 * n));
     HIP_TRY(bufs.alloc(&dout, 2 * n));
-    HIP_TRY(bufs.alloc(&dcol, 1));
-    HIP_TRY(hipMemcpy(dO, O, (size_t)3 * n * 8, hipMemcpyDefault));
-    HIP_TRY(hipMemcpy(dD, D, (size_t)3 * n * 8, hipMemcpyDefault));
-    HIP_TRY(hipMemcpy(dcol, col, sizeof(srt_collider), hipMemcpyDefault));
-    hipLaunchKernelGGL(k_intersect_one, dim3(grid_for(n, c->max_blocks)), dim3(BLOCK), 0, c->f->stream, dcol, dO, dD, n,
-                       dout);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->f->stream));
-    HIP_TRY(hipMemcpy(out, dout, (size_t)2 * n * 8, hipMemcpyDefault));
+    HIP_TRY(bufs.in(&dcol, col, 1));
+    if (int rc = run_kernel(c, n, nullptr, nullptr, k_intersect_one, dcol, dO, dD, n, dout)) return rc;
+    HIP_TRY(bufs.copy(out, dout, 2 * n));
     return SRT_OK;
 }
 
@@ -3226,23 +3279,18 @@ int srt_collider_surface(srt_ctx* c, const srt_collider* col, const double* P, i
         return fail(SRT_ERR_ARG, "Triangle uv is undefined in the reference (triangle.py:79-83)");
     if (n <= 0) return SRT_OK;
     HIP_TRY(hipSetDevice(c->device));
-    CallBufs bufs;
+    DevList bufs;
     srt_collider rec = *col;
     if (!primitive_uv) rec.flags &= ~SRT_CF_UV_CROSS;  // the collider's own 4x3 cross coordinates
     double *dP, *dN = nullptr, *duv = nullptr;
     srt_collider* dcol;
-    HIP_TRY(bufs.alloc(&dP, 3 * n));
+    HIP_TRY(bufs.in(&dP, P, 3 * n));
     if (N) HIP_TRY(bufs.alloc(&dN, 3 * n));
     if (uv) HIP_TRY(bufs.alloc(&duv, 2 * n));
-    HIP_TRY(bufs.alloc(&dcol, 1));
-    HIP_TRY(hipMemcpy(dP, P, (size_t)3 * n * 8, hipMemcpyDefault));
-    HIP_TRY(hipMemcpy(dcol, &rec, sizeof(srt_collider), hipMemcpyDefault));
-    hipLaunchKernelGGL(k_collider_surface, dim3(grid_for(n, c->max_blocks)), dim3(BLOCK), 0, c->f->stream, dcol, dP, n,
-                       dN, duv);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->f->stream));
-    if (N) HIP_TRY(hipMemcpy(N, dN, (size_t)3 * n * 8, hipMemcpyDefault));
-    if (uv) HIP_TRY(hipMemcpy(uv, duv, (size_t)2 * n * 8, hipMemcpyDefault));
+    HIP_TRY(bufs.in(&dcol, &rec, 1));
+    if (int rc = run_kernel(c, n, nullptr, nullptr, k_collider_surface, dcol, dP, n, dN, duv)) return rc;
+    if (N) HIP_TRY(bufs.copy(N, dN, 3 * n));
+    if (uv) HIP_TRY(bufs.copy(uv, duv, 2 * n));
     return SRT_OK;
 }
 
@@ -3253,32 +3301,25 @@ int srt_texture_lookup(srt_ctx* c, const srt_texture* tex, const uint8_t* texels
         return fail(SRT_ERR_ARG, "texture record outside the texel array");
     if (n <= 0) return SRT_OK;
     HIP_TRY(hipSetDevice(c->device));
-    CallBufs bufs;
+    DevList bufs;
     uint8_t* dtexels;
     srt_texture* dtex;
     double *duv, *drgb;
     uint32_t* dflags;
-    HIP_TRY(bufs.alloc(&dtexels, texel_bytes));
-    HIP_TRY(bufs.alloc(&dtex, 1));
-    HIP_TRY(bufs.alloc(&duv, 2 * n));
+    HIP_TRY(bufs.in(&dtexels, texels, texel_bytes));
+    HIP_TRY(bufs.in(&dtex, tex, 1));
+    HIP_TRY(bufs.in(&duv, uv, 2 * n));
     HIP_TRY(bufs.alloc(&drgb, 3 * n));
     HIP_TRY(bufs.alloc(&dflags, 1));
-    HIP_TRY(hipMemcpy(dtexels, texels, (size_t)texel_bytes, hipMemcpyDefault));
-    HIP_TRY(hipMemcpy(dtex, tex, sizeof(srt_texture), hipMemcpyDefault));
-    HIP_TRY(hipMemcpy(duv, uv, (size_t)2 * n * 8, hipMemcpyDefault));
     HIP_TRY(hipMemset(dflags, 0, 4));
     SceneView S{};
     S.tex = (const RT_RO srt_texture*)dtex;
     S.texels = (const RT_RO uint8_t*)dtexels;
     S.ntex = 1;
-    hipLaunchKernelGGL(k_texture_lookup, dim3(grid_for(n, c->max_blocks)), dim3(BLOCK), 0, c->f->stream, S, duv, n, drgb,
-                       dflags);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->f->stream));
-    uint32_t flags = 0;
-    HIP_TRY(hipMemcpy(&flags, dflags, 4, hipMemcpyDefault));
-    HIP_TRY(hipMemcpy(rgb, drgb, (size_t)3 * n * 8, hipMemcpyDefault));
-    return check_flags(flags);
+    int flag_rc = SRT_OK;
+    if (int rc = run_kernel(c, n, dflags, &flag_rc, k_texture_lookup, S, duv, n, drgb, dflags)) return rc;
+    HIP_TRY(bufs.copy(rgb, drgb, 3 * n));
+    return flag_rc;
 }
 
 int srt_material_normal(srt_ctx* c, const srt_collider* col, const srt_texture* normalmap, const uint8_t* texels,
@@ -3295,7 +3336,7 @@ int srt_material_normal(srt_ctx* c, const srt_collider* col, const srt_texture* 
     }
     if (n <= 0) return SRT_OK;
     HIP_TRY(hipSetDevice(c->device));
-    CallBufs bufs;
+    DevList bufs;
     srt_material mrec{};
     mrec.type = SRT_GLOSSY;
     mrec.tex = mrec.tex_aux0 = mrec.tex_aux1 = -1;
@@ -3306,59 +3347,44 @@ int srt_material_normal(srt_ctx* c, const srt_collider* col, const srt_texture* 
     uint8_t* dtexels = nullptr;
     double *dP, *dor, *dN;
     uint32_t* dflags;
-    HIP_TRY(bufs.alloc(&dcol, 1));
-    HIP_TRY(bufs.alloc(&dmat, 1));
-    HIP_TRY(bufs.alloc(&dP, 3 * n));
-    HIP_TRY(bufs.alloc(&dor, n));
+    HIP_TRY(bufs.in(&dcol, col, 1));
+    HIP_TRY(bufs.in(&dmat, &mrec, 1));
+    HIP_TRY(bufs.in(&dP, P, 3 * n));
+    HIP_TRY(bufs.in(&dor, orient, n));
     HIP_TRY(bufs.alloc(&dN, 3 * n));
     HIP_TRY(bufs.alloc(&dflags, 1));
-    HIP_TRY(hipMemcpy(dcol, col, sizeof(srt_collider), hipMemcpyDefault));
-    HIP_TRY(hipMemcpy(dmat, &mrec, sizeof(srt_material), hipMemcpyDefault));
-    HIP_TRY(hipMemcpy(dP, P, (size_t)3 * n * 8, hipMemcpyDefault));
-    HIP_TRY(hipMemcpy(dor, orient, (size_t)n * 8, hipMemcpyDefault));
     HIP_TRY(hipMemset(dflags, 0, 4));
     SceneView S{};
     if (normalmap) {
-        HIP_TRY(bufs.alloc(&dtex, 1));
-        HIP_TRY(bufs.alloc(&dtexels, texel_bytes));
-        HIP_TRY(hipMemcpy(dtex, normalmap, sizeof(srt_texture), hipMemcpyDefault));
-        HIP_TRY(hipMemcpy(dtexels, texels, (size_t)texel_bytes, hipMemcpyDefault));
+        HIP_TRY(bufs.in(&dtex, normalmap, 1));
+        HIP_TRY(bufs.in(&dtexels, texels, texel_bytes));
         S.tex = (const RT_RO srt_texture*)dtex;
         S.texels = (const RT_RO uint8_t*)dtexels;
         S.ntex = 1;
     }
-    hipLaunchKernelGGL(k_material_normal, dim3(grid_for(n, c->max_blocks)), dim3(BLOCK), 0, c->f->stream, S, dcol, dmat,
-                       dP, dor, n, dN, dflags);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->f->stream));
-    uint32_t flags = 0;
-    HIP_TRY(hipMemcpy(&flags, dflags, 4, hipMemcpyDefault));
-    HIP_TRY(hipMemcpy(N, dN, (size_t)3 * n * 8, hipMemcpyDefault));
-    return check_flags(flags);
+    int flag_rc = SRT_OK;
+    if (int rc = run_kernel(c, n, dflags, &flag_rc, k_material_normal, S, dcol, dmat, dP, dor, n, dN, dflags)) return rc;
+    HIP_TRY(bufs.copy(N, dN, 3 * n));
+    return flag_rc;
 }
 
 int srt_primary_rays(srt_ctx* c, const srt_camera* cam, const double* J, double* O, double* D) {
     if (!c || !cam || !J || !O || !D) return fail(SRT_ERR_ARG, "null argument");
     HIP_TRY(hipSetDevice(c->device));
-    CallBufs bufs;
+    DevList bufs;
     const int64_t n = (int64_t)cam->width * cam->height;
     double *dJ, *dO, *dD, *xs, *ys;
-    HIP_TRY(bufs.alloc(&dJ, 4 * n));
+    HIP_TRY(bufs.in(&dJ, J, 4 * n));
     HIP_TRY(bufs.alloc(&dO, 3 * n));
     HIP_TRY(bufs.alloc(&dD, 3 * n));
-    HIP_TRY(bufs.alloc(&xs, cam->width));
-    HIP_TRY(bufs.alloc(&ys, cam->height));
-    HIP_TRY(hipMemcpy(dJ, J, (size_t)4 * n * 8, hipMemcpyDefault));
-    HIP_TRY(hipMemcpy(xs, cam->xs, (size_t)cam->width * 8, hipMemcpyDefault));
-    HIP_TRY(hipMemcpy(ys, cam->ys, (size_t)cam->height * 8, hipMemcpyDefault));
+    HIP_TRY(bufs.in(&xs, cam->xs, cam->width));
+    HIP_TRY(bufs.in(&ys, cam->ys, cam->height));
     srt_camera k = *cam;
     k.xs = xs;
     k.ys = ys;
-    hipLaunchKernelGGL(k_primary_rays, dim3(grid_for(n, c->max_blocks)), dim3(BLOCK), 0, c->f->stream, k, dJ, n, dO, dD);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->f->stream));
-    HIP_TRY(hipMemcpy(O, dO, (size_t)3 * n * 8, hipMemcpyDefault));
-    HIP_TRY(hipMemcpy(D, dD, (size_t)3 * n * 8, hipMemcpyDefault));
+    if (int rc = run_kernel(c, n, nullptr, nullptr, k_primary_rays, k, dJ, n, dO, dD)) return rc;
+    HIP_TRY(bufs.copy(O, dO, 3 * n));
+    HIP_TRY(bufs.copy(D, dD, 3 * n));
     return SRT_OK;
 }
 
@@ -3401,7 +3427,7 @@ int srt_mt19937_uniforms(srt_ctx* c, const uint32_t* key, int32_t pos, int64_t n
     double* dst = out;
     const bool host_out = n_out > 0 && !is_device_ptr(out);
     if (host_out) {
-        if ((rc = ensure_buf(&c->mt_out, c->mt_out_cap, n_out))) return rc;
+        if ((rc = c->mt_out.ensure(n_out))) return rc;
         dst = c->mt_out;
     }
     hipStream_t st = c->f->stream;
@@ -3471,8 +3497,6 @@ int srt_comm_rank(srt_ctx* c, int* nranks, int* rank) {
 }
 
 }  // extern "C"
-static int render_group_once(srt_ctx** ctxs, int n, const srt_camera* cam, const srt_render_args* a, srt_stats* st);
-static int render_group_async(srt_ctx** ctxs, int n, const srt_camera* cam, const srt_render_args* a);
 
 // The gathers of all the group's contexts posted in one RCCL group, then the frame assembled on rank 0
 static int gather_group(srt_ctx** ctxs, int n) {
@@ -3512,43 +3536,6 @@ static int finish_group(srt_ctx** ctxs, int n, srt_stats& sum, int rc) {
     }
     return rc;
 }
-extern "C" {
-
-int srt_render_group(srt_ctx** ctxs, int n, const srt_camera* cam, const srt_render_args* a, srt_stats* st) {
-    if (!ctxs || n < 1 || !cam || !a) return fail(SRT_ERR_ARG, "null argument");
-    for (int q = 0; q < n; ++q)
-        if (!ctxs[q] || ctxs[q]->nranks != n || ctxs[q]->rank != q)
-            return fail(SRT_ERR_ARG, "contexts must be the ranks 0..n-1 of one srt_comm_init_all group");
-    for (int q = 0; q < n; ++q) ctxs[q]->pf.valid = false;
-    for (int q = 0; q < n; ++q)
-        if (ctxs[q]->has_scene && ctxs[q]->needs_inputs) return refuse_inputs_scene("srt_render_group");
-    if (a->jitter) return fail(SRT_ERR_ARG, "a group frame draws its jitter on the devices (mt or Philox)");
-    if (a->out_hit_id) return fail(SRT_ERR_ARG, "hit ids of a sharded frame are not gathered");
-    if (a->flags & ~(SRT_RENDER_ASYNC | SRT_RENDER_RGB_ROWS | SRT_RENDER_RGB_LOCAL))
-        return fail(SRT_ERR_ARG, "group flags: ASYNC, RGB_ROWS, RGB_LOCAL");
-    if ((a->flags & SRT_RENDER_RGB_LOCAL) && (a->out_rgb || (a->flags & SRT_RENDER_RGB_ROWS)))
-        return fail(SRT_ERR_ARG, "SRT_RENDER_RGB_LOCAL needs out_rgb NULL and no SRT_RENDER_RGB_ROWS");
-    if (a->flags & SRT_RENDER_ASYNC) return render_group_async(ctxs, n, cam, a);
-    // A frame whose passes overflowed a queue/ring, met a chain-mode tie or left the fixed-point range
-    // is rendered again on every context (the gather pairs the ranks' tiles), from the same numpy
-    // state, as the synchronous single-GPU path does; the contexts already grew their queues or
-    // dropped chain mode / fixed-point sums in finish_async.
-    srt_mt_state mt0{};
-    if (a->mt) mt0 = *a->mt;
-    int rc = SRT_OK;
-    for (int attempt = 0;; ++attempt) {
-        if (a->mt) *a->mt = mt0;
-        // (a flag left by an earlier frame must not make a failure of this one look retryable)
-        for (int q = 0; q < n; ++q) ctxs[q]->retry_frame = false;
-        rc = render_group_once(ctxs, n, cam, a, st);
-        bool again = false;
-        for (int q = 0; q < n; ++q) again |= ctxs[q]->retry_frame;
-        if (rc == SRT_OK && st) st->retries += attempt;  // frames rendered again, as srt_render counts them
-        if (rc == SRT_OK || !again || attempt >= 8) return rc;
-    }
-}
-
-}  // extern "C"
 
 static int render_group_once(srt_ctx** ctxs, int n, const srt_camera* cam, const srt_render_args* a, srt_stats* st) {
     const bool want_rgb = a->out_rgb != nullptr;
@@ -3607,6 +3594,41 @@ static int render_group_async(srt_ctx** ctxs, int n, const srt_camera* cam, cons
 }
 
 extern "C" {
+
+int srt_render_group(srt_ctx** ctxs, int n, const srt_camera* cam, const srt_render_args* a, srt_stats* st) {
+    if (!ctxs || n < 1 || !cam || !a) return fail(SRT_ERR_ARG, "null argument");
+    for (int q = 0; q < n; ++q)
+        if (!ctxs[q] || ctxs[q]->nranks != n || ctxs[q]->rank != q)
+            return fail(SRT_ERR_ARG, "contexts must be the ranks 0..n-1 of one srt_comm_init_all group");
+    for (int q = 0; q < n; ++q) ctxs[q]->pf.valid = false;
+    for (int q = 0; q < n; ++q)
+        if (ctxs[q]->has_scene && ctxs[q]->needs_inputs) return refuse_inputs_scene("srt_render_group");
+    if (a->jitter) return fail(SRT_ERR_ARG, "a group frame draws its jitter on the devices (mt or Philox)");
+    if (a->out_hit_id) return fail(SRT_ERR_ARG, "hit ids of a sharded frame are not gathered");
+    if (a->flags & ~(SRT_RENDER_ASYNC | SRT_RENDER_RGB_ROWS | SRT_RENDER_RGB_LOCAL))
+        return fail(SRT_ERR_ARG, "group flags: ASYNC, RGB_ROWS, RGB_LOCAL");
+    if ((a->flags & SRT_RENDER_RGB_LOCAL) && (a->out_rgb || (a->flags & SRT_RENDER_RGB_ROWS)))
+        return fail(SRT_ERR_ARG, "SRT_RENDER_RGB_LOCAL needs out_rgb NULL and no SRT_RENDER_RGB_ROWS");
+    if (a->flags & SRT_RENDER_ASYNC) return render_group_async(ctxs, n, cam, a);
+    // A frame whose passes overflowed a queue/ring, met a chain-mode tie or left the fixed-point range
+    // is rendered again on every context (the gather pairs the ranks' tiles), from the same numpy
+    // state, as the synchronous single-GPU path does; the contexts already grew their queues or
+    // dropped chain mode / fixed-point sums in finish_async.
+    srt_mt_state mt0{};
+    if (a->mt) mt0 = *a->mt;
+    int rc = SRT_OK;
+    for (int attempt = 0;; ++attempt) {
+        if (a->mt) *a->mt = mt0;
+        // (a flag left by an earlier frame must not make a failure of this one look retryable)
+        for (int q = 0; q < n; ++q) ctxs[q]->retry_frame = false;
+        rc = render_group_once(ctxs, n, cam, a, st);
+        bool again = false;
+        for (int q = 0; q < n; ++q) again |= ctxs[q]->retry_frame;
+        if (rc == SRT_OK && st) st->retries += attempt;  // frames rendered again, as srt_render counts them
+        if (rc == SRT_OK || !again || attempt >= 8) return rc;
+    }
+}
+
 
 int srt_render_group_finish(srt_ctx** ctxs, int n, srt_stats* st) {
     if (!ctxs || n < 1) return fail(SRT_ERR_ARG, "null argument");
@@ -3696,7 +3718,7 @@ int srt_debug_lane_stats(srt_ctx* c, int mode, int64_t* out, int n) {
     if (rc) return rc;
     const size_t bytes = (size_t)SRT_MAX_DEPTHS * 2 * sizeof(unsigned long long);
     if (mode == 1) {
-        if (!c->lane_stats) HIP_TRY(hipMalloc(&c->lane_stats, bytes));
+        if (!c->lane_stats) HIP_TRY(dalloc(&c->lane_stats, SRT_MAX_DEPTHS * 2));
         HIP_TRY(hipMemset(c->lane_stats, 0, bytes));
         return SRT_OK;
     }
@@ -3704,8 +3726,7 @@ int srt_debug_lane_stats(srt_ctx* c, int mode, int64_t* out, int n) {
     if (!c->lane_stats) return fail(SRT_ERR_ARG, "lane stats were not started");
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, c->lane_stats, (size_t)n * 2 * sizeof(int64_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipFree(c->lane_stats));
-    c->lane_stats = nullptr;
+    HIP_TRY(c->lane_stats.reset());
     return SRT_OK;
 }
 
@@ -3733,7 +3754,7 @@ int srt_debug_mt_residue(srt_ctx* c, int64_t* nonzero_words) {
     // (window 0 of a table holds a copy of the key, written by a plain store at every generation that
     // jumps -- never an XOR target -- and left there when no segment starts at the key: not counted)
     for (FrameSlot& f : c->slots)
-        if (f.mt_win && f.mt_win_cap > rtmt::N && (rc = count(f.mt_win + rtmt::N, f.mt_win_cap - rtmt::N))) return rc;
+        if (f.mt_win && f.mt_win.cap > rtmt::N && (rc = count(f.mt_win + rtmt::N, f.mt_win.cap - rtmt::N))) return rc;
     if (c->mt && (rc = count(mt_end_acc(c), rtmt::N + 1))) return rc;
     *nonzero_words = nz;
     return SRT_OK;

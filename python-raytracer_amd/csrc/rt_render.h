@@ -18,8 +18,8 @@ struct FrameNeeds {
 
 // whether the slot holds everything the frame needs (grow_slot would change nothing)
 bool slot_holds(const srt_ctx* c, const FrameSlot& f, const FrameNeeds& N) {
-#define X(b) N.b <= f.b##_cap &&
-    return SLOT_BUFFERS(X) N.mt_win <= f.mt_win_cap &&
+#define X(b) N.b <= f.b.cap &&
+    return SLOT_BUFFERS(X) N.mt_win <= f.mt_win.cap &&
 #undef X
            (!N.queue_rays || queue_seg_for(N.queue_rays) <= f.seg) &&
            (!N.ring_rays || (ring_cap_for(N.ring_rays) <= f.ring_cap && ring_slots(c) <= f.nslot)) &&
@@ -29,11 +29,11 @@ bool slot_holds(const srt_ctx* c, const FrameSlot& f, const FrameNeeds& N) {
 // grow the slot to what the frame needs (no frame is in flight on it)
 int grow_slot(srt_ctx* c, FrameSlot& f, const FrameNeeds& N) {
     int r = SRT_OK;
-    const int64_t had_g_u8 = f.g_u8_cap;
-#define X(b) if (!r && N.b > 0) r = ensure_buf(&f.b, f.b##_cap, N.b);
+    const int64_t had_g_u8 = f.g_u8.cap;
+#define X(b) if (!r && N.b > 0) r = f.b.ensure(N.b);
     SLOT_BUFFERS(X)
 #undef X
-    if (!r && N.g_u8_zeroed && f.g_u8_cap != had_g_u8 && hipMemset(f.g_u8, 0, (size_t)f.g_u8_cap) != hipSuccess)
+    if (!r && N.g_u8_zeroed && f.g_u8.cap != had_g_u8 && hipMemset(f.g_u8, 0, (size_t)f.g_u8.cap) != hipSuccess)
         r = fail(SRT_ERR_HIP, "hipMemset failed");
     if (!r && N.mt_win > 0) r = mt_win_ensure(c, f, N.mt_win);
     if (!r && N.queue_rays) r = ensure_queues(f, N.queue_rays);
@@ -236,12 +236,7 @@ struct RenderCall {
         // shapes drops them between frames, when no frame in flight reads them)
         if (c->async_pending == 0 && (c->mt_bandtabs.size() >= 16 || c->mt_end_polys.size() >= 64)) {
             HIP_TRY(hipDeviceSynchronize());
-            for (auto& t : c->mt_bandtabs) {
-                (void)hipFree(t.bands);
-                (void)hipFree(t.polys);
-            }
             c->mt_bandtabs.clear();
-            for (auto& e : c->mt_end_polys) (void)hipFree(e.second);
             c->mt_end_polys.clear();
         }
         // a whole frame with nothing in flight (synchronous, or the first of a pipeline): short segments in
@@ -299,13 +294,13 @@ struct RenderCall {
 
     // Camera tables (shared by the slots): room for them, then uploaded only when they change (a
     // render loop re-sends the same ones)
-    bool camera_tables_hold() const { return W <= c->cam_cap[0] && Hf <= c->cam_cap[1] && n_rows <= c->cam_cap[2]; }
+    bool camera_tables_hold() const { return W <= c->xs.cap && Hf <= c->ys.cap && n_rows <= c->rows.cap; }
     int upload_camera(hipStream_t st) {
         int rc;
         const void* old[3] = {c->xs, c->ys, c->rows};
-        if ((rc = ensure_buf(&c->xs, c->cam_cap[0], W))) return rc;
-        if ((rc = ensure_buf(&c->ys, c->cam_cap[1], Hf))) return rc;
-        if ((rc = ensure_buf(&c->rows, c->cam_cap[2], n_rows))) return rc;
+        if ((rc = c->xs.ensure(W))) return rc;
+        if ((rc = c->ys.ensure(Hf))) return rc;
+        if ((rc = c->rows.ensure(n_rows))) return rc;
         const void* now[3] = {c->xs, c->ys, c->rows};
         for (int k = 0; k < 3; ++k)
             if (old[k] != now[k]) c->cam_host[k].clear();
