@@ -78,6 +78,8 @@ enum {
 #define SRT_CF_SHADOW 1u   /* member of scene.shadowed_collider_list */
 #define SRT_CF_MC 2u       /* primitive.mc: Monte-Carlo refraction pick */
 #define SRT_CF_UV_CROSS 4u /* Cuboid/SkyBox primitive: uv /= (4, 3) */
+#define SRT_CF_VNORMAL 8u  /* Triangle: per-vertex normals in p[24..32], interpolated at the hit */
+#define SRT_CF_VUV 16u     /* Triangle: per-vertex (u, v) in p[33..38], interpolated at the hit */
 /* material flags */
 #define SRT_MF_ROUGH 1u    /* Glossy: roughness != 0 (specular lobe on) */
 #define SRT_MF_LIGHTMAP 2u /* SkyBox: light_intensity != 0 (lightmap on non-primary rays) */
@@ -98,7 +100,12 @@ enum {
  *            29 length, 30-38 inverse_basis_matrix (row-major), 39-41 (1/width,1/height,1/length),
  *            42 1.0 if basis_matrix is exactly the identity (else 0.0)
  *   TRIANGLE 0-2 centroid, 3-5 normal, 6-8 p1, 9-11 p2, 12-14 p3, 15-17 n31, 18-20 n12,
- *            21-23 n23
+ *            21-23 n23; with SRT_CF_VNORMAL / SRT_CF_VUV also 24-26 n1, 27-29 n2, 30-32 n3 (unit
+ *            vertex normals), 33-38 u1 v1 u2 v2 u3 v3, 39 d2 = dot(n31, p2 - p1), 40 d3 =
+ *            dot(n12, p3 - p2).  At a hit P: b2 = dot(n31, P - p1) / d2, b3 = dot(n12, P - p2) / d3,
+ *            b1 = (1 - b2) - b3; normal = normalize(n1*b1 + n2*b2 + n3*b3) (the face normal when
+ *            that sum is zero), u = u1*b1 + u2*b2 + u3*b3, v likewise.  Without the flags slots
+ *            24-47 are zero and unread.
  */
 typedef struct srt_collider {
     int32_t type;          /* SRT_SPHERE .. */
@@ -400,7 +407,8 @@ int srt_shade_level_inputs(srt_ctx* ctx, const srt_trace_args* args, const int32
 /* Collider.get_Normal (N [3][n]) and get_uv (uv [2][n], u then v) at points P [3][n] on the
  * collider; primitive_uv = 1 applies a Cuboid/SkyBox primitive's (4, 3) cross divide
  * (SRT_CF_UV_CROSS, cuboid.py:29-34), 0 returns the collider's own coordinates.  Either output may
- * be NULL.  Triangle uv is undefined in the reference (triangle.py:79-83): SRT_ERR_ARG. */
+ * be NULL.  The uv of a Triangle without SRT_CF_VUV is undefined in the reference
+ * (triangle.py:79-83): SRT_ERR_ARG. */
 int srt_collider_surface(srt_ctx* ctx, const srt_collider* collider, const double* P, int64_t n,
                          double* N, double* uv, int primitive_uv);
 /* image.get_color: the texel at uv [2][n] of the texture record `tex` over `texels`

@@ -92,17 +92,21 @@ constexpr uint32_t MAT_LDS_NARROW = 0x400u;  // ... in k_frame's 64-thread block
 // per-hit shading inputs (HitIn: a user texture's colour, a user light's distance and irradiance);
 // only k_shade_forced's srt_shade_level_inputs instantiations carry it, no variant of the host's tables
 constexpr uint32_t MAT_HITIN = 0x800u;
+// Triangle colliders with per-vertex normals / texture coordinates (SRT_CF_VNORMAL, SRT_CF_VUV): the
+// barycentric interpolation in collider_normal / collider_uv.  Bits 12..29 hold a collider sequence
+// (below), so this is the top bit; no sequence variant carries it (a sequence never holds triangles).
+constexpr uint32_t MAT_VATTR = 0x80000000u;
 constexpr uint32_t MAT_GENERIC = MAT_ALL | MAT_TRI | MAT_NMAP;
 constexpr uint32_t mat_bit(int type) { return 1u << type; }
-// Collider sequence known at compile time (bits 12..31 of a variant's feature mask, 0: the scene's
-// collider list read at run time): bits 0..3 of the sequence hold the count n (1..8), then 2 bits per
+// Collider sequence known at compile time (bits 12..29 of a variant's feature mask, 0: the scene's
+// collider list read at run time): bits 0..3 of the sequence hold the count n (1..7), then 2 bits per
 // collider its type (SRT_SPHERE .. SRT_TRIANGLE), collider 0 first.  A kernel instantiated for a
 // sequence intersects the colliders in straight-line code (no loop, no type switch: the compiler
 // shares common subexpressions between colliders and interleaves their independent arithmetic); the
 // host runs it only on scenes whose colliders have exactly those types in that order.
 constexpr int SEQ_SHIFT = 12;
-constexpr int SEQ_MAX = 8;
-constexpr uint32_t seq_of(uint32_t feat) { return feat >> SEQ_SHIFT; }
+constexpr int SEQ_MAX = 7;
+constexpr uint32_t seq_of(uint32_t feat) { return (feat & ~MAT_VATTR) >> SEQ_SHIFT; }
 constexpr int seq_count(uint32_t q) { return (int)(q & 15u); }
 constexpr int seq_type(uint32_t q, int k) { return (int)((q >> (4 + 2 * k)) & 3u); }
 // the sequence code of n collider types (n <= SEQ_MAX), 0 if it cannot be encoded
@@ -436,13 +440,33 @@ RT_HD d3 cuboid_normal(const RT_RO double* p, d3 P) {
     return axis ? s : matmul_rows(p + 30, s);
 }
 
+// Barycentric weights of P on a Triangle with per-vertex attributes (SRT_CF_VNORMAL / SRT_CF_VUV),
+// from the edge vectors of the record and the two denominators the host stored: b2 = dot(n31, P - p1)
+// / d2, b3 = dot(n12, P - p2) / d3, b1 = (1 - b2) - b3.  Plain divisions (exact, as the host's).
+RT_HD void triangle_bary(const RT_RO double* p, d3 P, double& b1, double& b2, double& b3) {
+    b2 = dot(ld3(p + 15), sub(P, ld3(p + 6))) / p[39];
+    b3 = dot(ld3(p + 18), sub(P, ld3(p + 9))) / p[40];
+    b1 = (1.0 - b2) - b3;
+}
+// normalize(n1*b1 + n2*b2 + n3*b3); the face normal when the sum is exactly zero
+RT_HD d3 triangle_vnormal(const RT_RO double* p, d3 P) {
+    double b1, b2, b3;
+    triangle_bary(p, P, b1, b2, b3);
+    const d3 s = add(add(mul(ld3(p + 24), b1), mul(ld3(p + 27), b2)), mul(ld3(p + 30), b3));
+    return is_zero(s) ? ld3(p + 3) : normalize(s);
+}
+
 // un-oriented collider normal at P (Collider.get_Normal)
+template <uint32_t FEAT = 0u>
 RT_HD d3 collider_normal(const RT_RO srt_collider& c, d3 P) {
     switch (c.type) {
         case SRT_SPHERE: return mul(sub(P, ld3(c.p)), c.p[4]);  // sphere.py:54-56
         case SRT_PLANE: return ld3(c.p + 3);                       // plane.py:104-105
         case SRT_CUBOID: return cuboid_normal(c.p, P);
-        default: return ld3(c.p + 3);                              // triangle.py:85-86
+        default:
+            if constexpr ((FEAT & MAT_VATTR) != 0)
+                if (c.flags & SRT_CF_VNORMAL) return triangle_vnormal(c.p, P);
+            return ld3(c.p + 3);                                   // triangle.py:85-86
     }
 }
 
@@ -474,6 +498,8 @@ RT_HD void cuboid_uv(const RT_RO double* p, d3 P, double& u, double& v) {
 }
 
 // Primitive.get_uv(hit) for the collider's primitive; returns false for the undefined Triangle uv
+// (a Triangle without SRT_CF_VUV, or a kernel variant without MAT_VATTR)
+template <uint32_t FEAT = 0u>
 RT_HD bool collider_uv(const RT_RO srt_collider& c, d3 P, double& u, double& v) {
     switch (c.type) {
         case SRT_SPHERE: {  // sphere.py:58-64
@@ -489,7 +515,17 @@ RT_HD bool collider_uv(const RT_RO srt_collider& c, d3 P, double& u, double& v) 
             break;
         }
         case SRT_CUBOID: cuboid_uv(c.p, P, u, v); break;
-        default: u = 0.0; v = 0.0; return false;
+        default:
+            if constexpr ((FEAT & MAT_VATTR) != 0) {
+                if (c.flags & SRT_CF_VUV) {  // u1*b1 + u2*b2 + u3*b3; no cross divide
+                    double b1, b2, b3;
+                    triangle_bary(c.p, P, b1, b2, b3);
+                    u = (c.p[33] * b1 + c.p[35] * b2) + c.p[37] * b3;
+                    v = (c.p[34] * b1 + c.p[36] * b2) + c.p[38] * b3;
+                    return true;
+                }
+            }
+            u = 0.0; v = 0.0; return false;
     }
     if (c.flags & SRT_CF_UV_CROSS) {  // cuboid.py:29-32, skybox.py:29-32
         u = u / 4.0;  // exact: a multiplication by 0.25
@@ -566,14 +602,14 @@ RT_HD d3 shading_normal(const SceneView& S, const RT_RO srt_collider& c, const R
                         double orient, uint32_t& err) {
     if ((FEAT & MAT_NMAP) && m.normalmap >= 0) {
         double u, v;
-        if (!collider_uv(c, P, u, v)) err |= ERR_UNSUPPORTED;
+        if (!collider_uv<FEAT>(c, P, u, v)) err |= ERR_UNSUPPORTED;
         const RT_RO srt_texture& T = S.tex[m.normalmap];
         const d3 t = texel_rgb(S, T, m.normalmap, tex_uv(S, T, u, v, err));
         d3 nm = d3{(t.x - 0.5) * 2.0, (t.y - 0.5) * 2.0, (t.z - 0.5) * 2.0};
         const RT_RO double* ib = (c.type == SRT_PLANE) ? c.p + 16 : c.p + 30;
         return mul(normalize(matmul_rows(ib, nm)), orient);
     }
-    return mul(collider_normal(c, P), orient);
+    return mul(collider_normal<FEAT>(c, P), orient);
 }
 
 // ---- counter-based RNG (Philox4x32-10) for Monte-Carlo shading and device jitter -------------
@@ -1151,7 +1187,7 @@ RT_HD void shade_glossy(const SceneView& S, const RT_RO srt_collider& c, int mi,
     uint32_t tw = 0u;
     if (m.tex >= 0) {
         double u, v;
-        if (!collider_uv(c, P, u, v)) err |= ERR_UNSUPPORTED;
+        if (!collider_uv<FEAT>(c, P, u, v)) err |= ERR_UNSUPPORTED;
         tw = texel_word(S, S.tex[m.tex], tex_uv(S, S.tex[m.tex], u, v, err));
     }
     RT_ACC(4, tg0);
@@ -1345,7 +1381,7 @@ RT_HD void shade_thinfilm(const SceneView& S, const RT_RO srt_collider& c, int m
     int64_t ti;
     if (m.flags & SRT_MF_NOISE) {
         double u, v;
-        if (!collider_uv(c, P, u, v)) err |= ERR_UNSUPPORTED;
+        if (!collider_uv<FEAT>(c, P, u, v)) err |= ERR_UNSUPPORTED;
         const RT_RO srt_texture& nt = S.tex[m.tex_aux1];
         double nz = tex_lut(S, m.tex_aux1, *tex_uv(S, nt, u, v, err));
         double thick = m.p[0] + m.p[1] * (nz - 0.5);
@@ -1436,7 +1472,7 @@ RT_HD void shade_emissive(const SceneView& S, const RT_RO srt_collider& c, int m
     if (m.tex >= 0) {
         double u, v;
         d3 P = add(r.o, mul(r.d, t));
-        if (!collider_uv(c, P, u, v)) err |= ERR_UNSUPPORTED;
+        if (!collider_uv<FEAT>(c, P, u, v)) err |= ERR_UNSUPPORTED;
         em.local(tex_rgb(S, m.tex, u, v, err));
     } else {
         em.local(ld3(m.p));
@@ -1455,7 +1491,7 @@ RT_HD void shade_diffuse(const SceneView& S, const RT_RO srt_collider& c, int mi
     d3 diff;
     if (m.tex >= 0) {
         double u, v;
-        if (!collider_uv(c, P, u, v)) err |= ERR_UNSUPPORTED;
+        if (!collider_uv<FEAT>(c, P, u, v)) err |= ERR_UNSUPPORTED;
         diff = tex_rgb(S, m.tex, u, v, err);
     } else {
         diff = ld3(m.p);
@@ -1556,7 +1592,7 @@ RT_HD void shade_hit(const SceneView& S, int cid, int mi, const Ray& r, double t
             if (MATS & mat_bit(SRT_DIFFUSE)) shade_diffuse<MATS>(S, c, mi, r, t, orient, em, err);
             break;
         case SRT_EMISSIVE:
-            if (MATS & mat_bit(SRT_EMISSIVE)) shade_emissive(S, c, mi, r, t, em, err);
+            if (MATS & mat_bit(SRT_EMISSIVE)) shade_emissive<MATS & MAT_VATTR>(S, c, mi, r, t, em, err);
             break;
         default:
             if (MATS & mat_bit(SRT_SKY)) shade_sky(S, c, mi, r, t, em, err);

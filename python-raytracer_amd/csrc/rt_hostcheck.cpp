@@ -28,6 +28,7 @@ struct Scene {
 
 thread_local BvhBuild g_bvh;  // the BVH of the scene of the current call
 thread_local int g_use_bvh = 1;
+thread_local bool g_vattr = false;  // the scene of the current call has SRT_CF_VNORMAL / SRT_CF_VUV triangles
 // rows of the current hc_render (null: identity / hc_trace): Monte-Carlo draws are keyed by the
 // global pixel, as key_pix in rt_kernels.hip
 thread_local const int32_t* g_rows = nullptr;
@@ -60,8 +61,13 @@ SceneView view_of(const srt_scene_desc* d) {
     S.nmedia = d->n_media; S.nimp = d->n_importance;
     S.sky_col = sky_collider(d->colliders, d->n_colliders, d->materials);
     S.nshadow = 0;
-    for (int i = 0; i < d->n_colliders; ++i)
+    g_vattr = false;
+    for (int i = 0; i < d->n_colliders; ++i) {
         if (d->colliders[i].flags & SRT_CF_SHADOW) S.nshadow++;
+        // (the feature scan of srt_upload_scene: the shaders' MAT_VATTR instantiation)
+        if (d->colliders[i].type == SRT_TRIANGLE && (d->colliders[i].flags & (SRT_CF_VNORMAL | SRT_CF_VUV)))
+            g_vattr = true;
+    }
     for (int k = 0; k < 3; ++k) S.ambient[k] = d->ambient[k];
     return S;
 }
@@ -117,27 +123,35 @@ double mc_uniform(const SceneView& S, uint64_t seed, int depth, const Ray& r, in
     return g.one();
 }
 
-void trace_one(const SceneView& S, const Ray& r, int depth, uint64_t seed, std::vector<Ray>& next, double* fb,
-               int64_t npix, uint32_t& err, int64_t& shadow, int32_t* hit_slot) {
+template <uint32_t MATS>
+void trace_one_feat(const SceneView& S, const Ray& r, int depth, uint64_t seed, std::vector<Ray>& next, double* fb,
+                    int64_t npix, uint32_t& err, int64_t& shadow, int32_t* hit_slot) {
     double t, o;
     bool ties;
     int id = nearest_hit(S, r.o, r.d, t, o, ties);
     if (hit_slot) *hit_slot = id;
     if (id < 0) return;
     HostEmit em{S, r, next, fb, npix, seed, depth, 0u, &shadow};
-    shade_hit<MAT_GENERIC | MAT_BVH>(S, id, S.col[id].material, r, t, o, em, err, mc_uniform(S, seed, depth, r, id, 0));
+    shade_hit<MATS>(S, id, S.col[id].material, r, t, o, em, err, mc_uniform(S, seed, depth, r, id, 0));
     if (ties) {
         uint32_t round = 1;
         for (int c = id + 1; c < S.ncol; ++c) {
             double oc;
             if (collider_hit(S.col[c], r.o, r.d, oc) == t) {
                 HostEmit et{S, r, next, fb, npix, seed, depth, round, &shadow};
-                shade_hit<MAT_GENERIC | MAT_BVH>(S, c, S.col[c].material, r, t, oc, et, err,
-                                             mc_uniform(S, seed, depth, r, c, round));
+                shade_hit<MATS>(S, c, S.col[c].material, r, t, oc, et, err, mc_uniform(S, seed, depth, r, c, round));
                 ++round;
             }
         }
     }
+}
+
+void trace_one(const SceneView& S, const Ray& r, int depth, uint64_t seed, std::vector<Ray>& next, double* fb,
+               int64_t npix, uint32_t& err, int64_t& shadow, int32_t* hit_slot) {
+    if (g_vattr)
+        trace_one_feat<MAT_GENERIC | MAT_BVH | MAT_VATTR>(S, r, depth, seed, next, fb, npix, err, shadow, hit_slot);
+    else
+        trace_one_feat<MAT_GENERIC | MAT_BVH>(S, r, depth, seed, next, fb, npix, err, shadow, hit_slot);
 }
 
 int err_code(uint32_t e) {
@@ -277,6 +291,28 @@ int hc_intersect_collider(const srt_collider* c, const double* O, const double* 
         double o;
         out[i] = collider_hit(*c, d3{O[i], O[n + i], O[2 * n + i]}, d3{D[i], D[n + i], D[2 * n + i]}, o);
         out[n + i] = o;
+    }
+    return SRT_OK;
+}
+
+// k_collider_surface: Collider.get_Normal (N [3][n]) and get_uv (uv [2][n]) at points P [3][n]; the uv of
+// a Triangle without SRT_CF_VUV is undefined (SRT_ERR_ARG, as srt_collider_surface)
+int hc_collider_surface(const srt_collider* c, const double* P, int64_t n, double* N, double* uv) {
+    if (uv && c->type == SRT_TRIANGLE && !(c->flags & SRT_CF_VUV)) {
+        g_err = "Triangle uv is undefined in the reference (triangle.py:79-83)";
+        return SRT_ERR_ARG;
+    }
+    for (int64_t i = 0; i < n; ++i) {
+        const d3 p = d3{P[i], P[n + i], P[2 * n + i]};
+        if (N) {
+            const d3 v = collider_normal<MAT_VATTR>(*c, p);
+            N[i] = v.x; N[n + i] = v.y; N[2 * n + i] = v.z;
+        }
+        if (uv) {
+            double u = 0.0, v = 0.0;
+            collider_uv<MAT_VATTR>(*c, p, u, v);
+            uv[i] = u; uv[n + i] = v;
+        }
     }
     return SRT_OK;
 }

@@ -974,11 +974,46 @@ struct FrameEmit {
     }
 };
 
+// FrameEmit for the k_frame variants that sum in fixed point when the frame does (P.fbx set; the
+// MAT_VATTR variants): the tile's sums are integers in acc's words
+struct FrameEmitFx : FrameEmit {
+    __device__ void local(d3 c) const {
+        if (!P.fbx) return FrameEmit::local(c);
+        if (is_zero(c)) return;
+        const uint32_t k = frame_tile_index(tiled, r.pix - tile0, (uint32_t)P.cam.width);
+        // fb_add's terms: each rounded to a multiple of 2^-FX_BITS and added as an integer, so the
+        // tile's totals do not depend on the ring's order and equal the per-depth kernels' bit for
+        // bit.  A term of magnitude >= 2^17 (or NaN) is left out, and a partial sum of magnitude >= 2^61
+        // scaled (2^17 in colour units) is distrusted: every term is below 2^61 scaled, so no sum wraps
+        // without landing there first.  Either renders the frame again in f64 (as does a total the
+        // resolve of the other paths would distrust, fx_suspect: k_frame's end).
+        const d3 t = mul(r.w, c);
+        bool ok = ((fabs(t.x) + fabs(t.y)) + fabs(t.z)) < FX_MAX;
+        if (ok) {
+            const double tv[3] = {t.x, t.y, t.z};
+            for (int ch = 0; ch < 3; ++ch) {
+                const unsigned long long add = (unsigned long long)__double2ll_rn(tv[ch] * FX_SCALE);
+                const unsigned long long old = __hip_atomic_fetch_add(
+                    reinterpret_cast<unsigned long long*>(&L->acc[ch][k]), add, __ATOMIC_RELAXED,
+                    __HIP_MEMORY_SCOPE_WORKGROUP);
+                const long long sum = (long long)(old + add);
+                ok &= sum < (1ll << 61) && sum >= -(1ll << 61);
+            }
+        }
+        if (!ok) atomicOr(&P.flags[1], RETRY_FIXED_RANGE);
+    }
+};
+
 template <uint32_t MATS, int OCC = 2>
 __global__ __launch_bounds__(FRAME_BLOCK, OCC) void k_frame(TraceParams P0) {
     constexpr bool FRAME_TILE = frame_tile_for(MATS), FRAME_LIFO = frame_lifo_for(MATS);
     constexpr bool FRAME_SPLIT = frame_split_for(MATS);
+    // The variants for per-vertex attributes sum a tile's colours as the per-depth kernels do, in fixed
+    // point (FrameEmitFx::local), when the frame does (P.fbx set): their frames are then the per-depth
+    // kernels' bit for bit.  The other variants keep their float64 sums in the ring's order.
+    constexpr bool FRAME_FX_VARIANT = (MATS & MAT_VATTR) != 0;
     const TraceParams& P = P0;
+    const bool frame_fx = FRAME_FX_VARIANT && P0.fbx != nullptr;
     {
         const int nl = P.S.nlut_lds;
         for (int i = threadIdx.x; i < nl * 256; i += FRAME_BLOCK) rt_lds_dyn[i] = P.S.tex[i >> 8].lut[i & 255];
@@ -1096,11 +1131,25 @@ __global__ __launch_bounds__(FRAME_BLOCK, OCC) void k_frame(TraceParams P0) {
             if ((int)depth > P.dcap) active = false;
         }
         RT_T0(tt2);
-        trace_one<MATS>(P, r, active, err, hs, FrameEmit{P, r, 0u, &shadow, &L, tile0, ring_base, FRAME_TILE, FRAME_SPLIT});
+        if constexpr (FRAME_FX_VARIANT)
+            trace_one<MATS>(P, r, active, err, hs,
+                            FrameEmitFx{{P, r, 0u, &shadow, &L, tile0, ring_base, FRAME_TILE, FRAME_SPLIT}});
+        else
+            trace_one<MATS>(P, r, active, err, hs, FrameEmit{P, r, 0u, &shadow, &L, tile0, ring_base, FRAME_TILE, FRAME_SPLIT});
         RT_ACC(17, tt2);
     }
     RT_T0(te0);
-    // tile pixels out
+    // tile pixels out (fixed-point sums: sum 2^-FX_BITS, fx_value's conversion)
+    if (frame_fx) {
+        __syncthreads();
+        bool bad = false;
+        for (int k = 0; k < 3; ++k) {
+            const unsigned long long w = *reinterpret_cast<unsigned long long*>(&L.acc[k][lane]);
+            bad |= (w >> 61) != 0;
+            L.acc[k][lane] = (double)(long long)w * FX_UNIT;
+        }
+        if (bad) atomicOr(&P.flags[1], RETRY_FIXED_RANGE);
+    }
     if (P.fuse_resolve) {
         uint8_t px[3] = {0, 0, 0};
         if (pact) {
@@ -1179,6 +1228,8 @@ constexpr uint32_t LDS_STK = RT_BVH_LDS_STACK ? MAT_LDS_STACK : 0u, LDS_STK_FRAM
 #define RT_MESH_FUSE_OCC RT_FUSE_OCC  // the glossy BVH variant's fused k_primary
 #endif
 constexpr uint32_t MATS_MESH = MATS_GLOSSY_SKY | MAT_TRI | MAT_BVH;  // a glossy TriangleMesh in the ex1 setting
+constexpr uint32_t MATS_MESH_VATTR = MATS_MESH | MAT_VATTR;                // ... smooth-shaded / textured
+constexpr uint32_t MATS_BVH_VATTR = MAT_GENERIC | MAT_BVH | MAT_VATTR;
 const Variant VARIANTS[] = {
     {MATS_GLOSSY_SKY, k_primary<MATS_GLOSSY_SKY, OCC>, k_trace<MATS_GLOSSY_SKY, OCC>, k_frame<MATS_GLOSSY_SKY, OCC>, k_trace<MATS_GLOSSY_SKY, OCC, true>,
      k_primary<MATS_GLOSSY_SKY, RT_FUSE_OCC, true>, k_primary_lean<MATS_GLOSSY_SKY, RT_FUSE_OCC>,
@@ -1195,6 +1246,15 @@ const Variant VARIANTS[] = {
     // scenes with a triangle BVH (TriangleMesh)
     {MAT_GENERIC | MAT_BVH, k_primary<MAT_GENERIC | MAT_BVH | LDS_STK, OCC>, k_trace<MAT_GENERIC | MAT_BVH | LDS_STK, OCC>,
      k_frame<MAT_GENERIC | MAT_BVH | LDS_STK_FRAME, OCC>, k_trace<MAT_GENERIC | MAT_BVH | LDS_STK, OCC, true>},
+    // Triangles with per-vertex normals / texture coordinates (MAT_VATTR, set by no scene without them, so
+    // these stay behind every variant above): the glossy mesh, the linear triangle loop, the BVH
+    {MATS_MESH_VATTR, k_primary<MATS_MESH_VATTR | LDS_STK, OCC>, k_trace<MATS_MESH_VATTR | LDS_STK, OCC>,
+     k_frame<MATS_MESH_VATTR | LDS_STK_FRAME, OCC>, k_trace<MATS_MESH_VATTR | LDS_STK, OCC, true>,
+     k_primary<MATS_MESH_VATTR | LDS_STK, RT_MESH_FUSE_OCC, true>},
+    {MAT_GENERIC | MAT_VATTR, k_primary<MAT_GENERIC | MAT_VATTR, OCC>, k_trace<MAT_GENERIC | MAT_VATTR, OCC>,
+     k_frame<MAT_GENERIC | MAT_VATTR, OCC>, k_trace<MAT_GENERIC | MAT_VATTR, OCC, true>},
+    {MATS_BVH_VATTR, k_primary<MATS_BVH_VATTR | LDS_STK, OCC>, k_trace<MATS_BVH_VATTR | LDS_STK, OCC>,
+     k_frame<MATS_BVH_VATTR | LDS_STK_FRAME, OCC>, k_trace<MATS_BVH_VATTR | LDS_STK, OCC, true>},
 #endif
 };
 // Variants for scenes of a given collider sequence (rt_device.h seq_of: the colliders intersected in
@@ -1371,14 +1431,14 @@ __global__ __launch_bounds__(BLOCK) void k_collider_surface(const srt_collider* 
     for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
         const d3 p = d3{P[i], P[n + i], P[2 * n + i]};
         if (N) {
-            const d3 v = collider_normal(*c, p);
+            const d3 v = collider_normal<MAT_VATTR>(*c, p);
             N[i] = v.x;
             N[n + i] = v.y;
             N[2 * n + i] = v.z;
         }
         if (uv) {
             double u = 0.0, v = 0.0;
-            collider_uv(*c, p, u, v);
+            collider_uv<MAT_VATTR>(*c, p, u, v);
             uv[i] = u;
             uv[n + i] = v;
         }
@@ -1396,7 +1456,7 @@ __global__ __launch_bounds__(BLOCK) void k_material_normal(SceneView S, const sr
     const RT_RO srt_material* m = (const RT_RO srt_material*)m_generic;
     uint32_t err = 0;
     for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
-        const d3 v = shading_normal(S, *c, *m, d3{P[i], P[n + i], P[2 * n + i]}, orient[i], err);
+        const d3 v = shading_normal<MAT_GENERIC | MAT_VATTR>(S, *c, *m, d3{P[i], P[n + i], P[2 * n + i]}, orient[i], err);
         N[i] = v.x;
         N[n + i] = v.y;
         N[2 * n + i] = v.z;
@@ -2905,6 +2965,9 @@ static void derive_scene_facts(srt_ctx* c, const srt_scene_desc* d, const SceneV
     if (lin_tri) c->mats |= MAT_TRI;  // Triangle colliders outside the BVH
     for (int i = 0; i < d->n_materials; ++i)
         if (d->materials[i].normalmap >= 0) c->mats |= MAT_NMAP;
+    for (int i = 0; i < d->n_colliders; ++i)
+        if (d->colliders[i].type == SRT_TRIANGLE && (d->colliders[i].flags & (SRT_CF_VNORMAL | SRT_CF_VUV)))
+            c->mats |= MAT_VATTR;
     c->seq = 0;
     if (S.bvh_nodes == 0 && d->n_colliders <= SEQ_MAX) {
         int types[SEQ_MAX];
@@ -3050,13 +3113,17 @@ int trace_impl(srt_ctx* c, const srt_trace_args* a, const int32_t* fid, const do
                 P.force_id = dfid;
                 P.force_t = dft;
                 P.force_o = dfo;
+                const bool bvh = (c->mats & MAT_BVH) != 0, va = (c->mats & MAT_VATTR) != 0;
                 if (in) {
                     const HitPtrs H{dalb, dldist, dlirr};
-                    hipLaunchKernelGGL((c->mats & MAT_BVH) ? k_shade_forced_inputs<MAT_GENERIC | MAT_BVH | MAT_HITIN>
-                                                           : k_shade_forced_inputs<MAT_GENERIC | MAT_HITIN>,
+                    hipLaunchKernelGGL(va ? (bvh ? k_shade_forced_inputs<MATS_BVH_VATTR | MAT_HITIN>
+                                                 : k_shade_forced_inputs<MAT_GENERIC | MAT_VATTR | MAT_HITIN>)
+                                          : (bvh ? k_shade_forced_inputs<MAT_GENERIC | MAT_BVH | MAT_HITIN>
+                                                 : k_shade_forced_inputs<MAT_GENERIC | MAT_HITIN>),
                                        dim3(trace_grid(c)), dim3(BLOCK), lut_bytes(c), c->f->stream, P, H);
                 } else {
-                    hipLaunchKernelGGL((c->mats & MAT_BVH) ? k_shade_forced<MAT_GENERIC | MAT_BVH> : k_shade_forced<MAT_GENERIC>,
+                    hipLaunchKernelGGL(va ? (bvh ? k_shade_forced<MATS_BVH_VATTR> : k_shade_forced<MAT_GENERIC | MAT_VATTR>)
+                                          : (bvh ? k_shade_forced<MAT_GENERIC | MAT_BVH> : k_shade_forced<MAT_GENERIC>),
                                        dim3(trace_grid(c)), dim3(BLOCK), lut_bytes(c), c->f->stream, P);
                 }
                 P.force_id = nullptr;
@@ -3275,7 +3342,7 @@ int srt_collider_surface(srt_ctx* c, const srt_collider* col, const double* P, i
                          int primitive_uv) {
     if (!c || !col || !P || (!N && !uv)) return fail(SRT_ERR_ARG, "null argument");
     if (col->type < 0 || col->type > 3) return fail(SRT_ERR_ARG, "bad collider type");
-    if (uv && col->type == SRT_TRIANGLE)
+    if (uv && col->type == SRT_TRIANGLE && !(col->flags & SRT_CF_VUV))
         return fail(SRT_ERR_ARG, "Triangle uv is undefined in the reference (triangle.py:79-83)");
     if (n <= 0) return SRT_OK;
     HIP_TRY(hipSetDevice(c->device));

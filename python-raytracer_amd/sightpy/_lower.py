@@ -308,6 +308,18 @@ def collider_record(c):
         p[15:18] = _f3(c.n31)
         p[18:21] = _f3(c.n12)
         p[21:24] = _f3(c.n23)
+        normals, uvs = getattr(c, "normals", None), getattr(c, "uvs", None)
+        if normals is not None or uvs is not None:
+            # per-vertex attributes (include/sightpy_rt.h): the device interpolates them with
+            # b2 = dot(n31, P - p1) / d2, b3 = dot(n12, P - p2) / d3, b1 = (1 - b2) - b3
+            if normals is not None:
+                rec["flags"] |= N.CF_VNORMAL
+                for k, n in enumerate(normals):
+                    p[24 + 3 * k:27 + 3 * k] = _f3(n)
+            if uvs is not None:
+                rec["flags"] |= N.CF_VUV
+                p[33:39] = [float(x) for uv in uvs for x in uv]
+            p[39], p[40] = (float(d) for d in c.bary_denominators())
     else:
         raise NotImplementedError(
             "collider type %s has no device kernel (sightpy on MI355X has no CPU fallback)" % type(c).__name__
@@ -476,7 +488,7 @@ def lower_scene(scene, extra_media=()):
         rec = collider_record(c)
         rec["material"] = mat_index[id(prim.material)]
         rec["max_ray_depth"] = int(prim.max_ray_depth)
-        flags = 0
+        flags = int(rec["flags"])  # (a Triangle's CF_VNORMAL / CF_VUV)
         if id(c) in shadow_ids:
             flags |= N.CF_SHADOW
         if getattr(prim, "mc", False):
@@ -486,9 +498,12 @@ def lower_scene(scene, extra_media=()):
         rec["flags"] = flags
         rec["primitive"] = prim_index.setdefault(id(prim), len(prim_index))
         m = prim.material
+        # a Triangle with its own texture coordinates (CF_VUV) takes an image texture; a normal map
+        # needs an inverse_basis_matrix and the thin film's noise a uv the reference leaves undefined
         if isinstance(c, Triangle_Collider) and (
             getattr(m, "normalmap_u8", None) is not None
-            or (isinstance(getattr(m, "diff_texture", None), image) and user_texture(m) is None)
+            or (isinstance(getattr(m, "diff_texture", None), image) and user_texture(m) is None
+                and not flags & N.CF_VUV)
             or isinstance(m, ThinFilmInterference)
         ):
             raise NotImplementedError("Triangle uv is undefined in the reference (triangle.py:79-83)")

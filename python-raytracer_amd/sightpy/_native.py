@@ -24,6 +24,7 @@ SRT_MATERIAL_PARAMS = 16
 SPHERE, PLANE, CUBOID, TRIANGLE = 0, 1, 2, 3
 GLOSSY, REFRACTIVE, THINFILM, DIFFUSE, EMISSIVE, SKY = 0, 1, 2, 3, 4, 5
 CF_SHADOW, CF_MC, CF_UV_CROSS = 1, 2, 4
+CF_VNORMAL, CF_VUV = 8, 16  # Triangle: per-vertex normals / texture coordinates in the record
 MF_ROUGH, MF_LIGHTMAP, MF_NOISE, MF_HIT_ALBEDO = 1, 2, 4, 8
 LIGHT_DIRECTIONAL, LIGHT_POINT, LIGHT_USER = 0, 1, 2
 
