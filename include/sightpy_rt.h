@@ -51,7 +51,7 @@
 extern "C" {
 #endif
 
-#define SRT_ABI_VERSION 6
+#define SRT_ABI_VERSION 7
 
 /* ---- error codes ------------------------------------------------------------------------ */
 #define SRT_OK 0
@@ -165,15 +165,30 @@ typedef struct srt_texture {
 
 /* SRT_LIGHT_USER: a user Light subclass.  dir = its get_L() (one direction for every hit), color
  * unused: get_distance and get_irradiance arrive per hit (srt_hit_inputs).  Its light_local rows are
- * filled as a directional light's. */
-enum { SRT_LIGHT_DIRECTIONAL = 0, SRT_LIGHT_POINT = 1, SRT_LIGHT_USER = 2 };
+ * filled as a directional light's.
+ * SRT_LIGHT_POSITIONAL: a PositionalLight / SpotLight at `pos`.  At a Glossy hit P (the un-nudged hit
+ * point), in float64 and in this order:
+ *   d = pos - P, dist = sqrt(d.d), L = d * (1.0 / dist), NdotL = max(N.L, 0),
+ *   irradiance = color * NdotL / (dist * dist) * intensity
+ * and with SRT_LF_SPOT further times s*s*(3 - 2*s), s = clip((c - cos_outer) / (cos_inner - cos_outer),
+ * 0, 1), c = (-L).axis.  The shadow ray leaves the nudged point along L and stops at the light: an
+ * occluder at a distance >= dist does not shadow.  Its light_local rows are zero and unread (cuboids
+ * rotate the per-hit direction themselves). */
+enum { SRT_LIGHT_DIRECTIONAL = 0, SRT_LIGHT_POINT = 1, SRT_LIGHT_USER = 2, SRT_LIGHT_POSITIONAL = 3 };
+/* light flags */
+#define SRT_LF_SPOT 1u /* POSITIONAL: the cone factor of a SpotLight (axis, cos_inner, cos_outer) */
 typedef struct srt_light {
     int32_t type;
-    int32_t reserved;
+    uint32_t flags; /* SRT_LF_* */
     double dir[3]; /* DirectionalLight.Ldir (normalised by Scene.add_DirectionalLight); USER: get_L() */
     double color[3];
-    double pos[3]; /* PointLight.pos (kept for the record: shading a Glossy hit under a point light
-                      fails with SRT_ERR_NAME, as the reference raises NameError) */
+    double pos[3]; /* POSITIONAL: the light's position.  PointLight.pos (kept for the record: shading a
+                      Glossy hit under a point light fails with SRT_ERR_NAME, as the reference raises
+                      NameError) */
+    double axis[3];   /* SRT_LF_SPOT: unit vector along the cone, pointing away from the light */
+    double cos_inner; /* SRT_LF_SPOT: cosine of the half-angle inside which the factor is 1 */
+    double cos_outer; /* SRT_LF_SPOT: cosine of the half-angle outside which it is 0 */
+    double intensity; /* POSITIONAL */
 } srt_light;
 
 typedef struct srt_scene_desc {

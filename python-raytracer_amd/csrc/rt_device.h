@@ -96,6 +96,10 @@ constexpr uint32_t MAT_HITIN = 0x800u;
 // barycentric interpolation in collider_normal / collider_uv.  Bits 12..29 hold a collider sequence
 // (below), so this is the top bit; no sequence variant carries it (a sequence never holds triangles).
 constexpr uint32_t MAT_VATTR = 0x80000000u;
+// SRT_LIGHT_POSITIONAL lights (PositionalLight, SpotLight): shade_glossy's light direction, distance
+// and irradiance per hit, its shadow rays along that direction up to the light.  Bit 30, the one left
+// above the collider sequence; no sequence variant carries it.
+constexpr uint32_t MAT_PLIGHT = 0x40000000u;
 constexpr uint32_t MAT_GENERIC = MAT_ALL | MAT_TRI | MAT_NMAP;
 constexpr uint32_t mat_bit(int type) { return 1u << type; }
 // Collider sequence known at compile time (bits 12..29 of a variant's feature mask, 0: the scene's
@@ -106,7 +110,7 @@ constexpr uint32_t mat_bit(int type) { return 1u << type; }
 // host runs it only on scenes whose colliders have exactly those types in that order.
 constexpr int SEQ_SHIFT = 12;
 constexpr int SEQ_MAX = 7;
-constexpr uint32_t seq_of(uint32_t feat) { return (feat & ~MAT_VATTR) >> SEQ_SHIFT; }
+constexpr uint32_t seq_of(uint32_t feat) { return (feat & ~(MAT_VATTR | MAT_PLIGHT)) >> SEQ_SHIFT; }
 constexpr int seq_count(uint32_t q) { return (int)(q & 15u); }
 constexpr int seq_type(uint32_t q, int k) { return (int)((q >> (4 + 2 * k)) & 3u); }
 // the sequence code of n collider types (n <= SEQ_MAX), 0 if it cannot be encoded
@@ -249,12 +253,44 @@ RT_HD cplx csqrt_np(cplx z) {
 }
 
 // ---- scene view ---------------------------------------------------------------------------
+// The light table as the kernels read it: n records of the fields every light has (80 bytes: the stride
+// the shaders' light loops were built with; the kernels without MAT_PLIGHT read nothing else, and
+// compile to what they were before srt_light grew), then n rows of six doubles that only a positional
+// light's shading reads (the extension rows: axis, cos_inner, cos_outer, intensity).  pack_lights lays
+// an srt_light table out this way (the same bytes in all: 128 per light).
+struct DevLight {
+    int32_t type;
+    uint32_t flags;
+    double dir[3];
+    double color[3];
+    double pos[3];
+};
+constexpr int LIGHT_EXT = 6;
+static_assert(sizeof(DevLight) == 80 && sizeof(DevLight) + LIGHT_EXT * sizeof(double) == sizeof(srt_light), "light table layout");
+inline void pack_lights(const srt_light* in, int n, void* out) {
+    DevLight* rec = static_cast<DevLight*>(out);
+    double* ext = reinterpret_cast<double*>(rec + n);
+    for (int i = 0; i < n; ++i) {
+        rec[i].type = in[i].type;
+        rec[i].flags = in[i].flags;
+        for (int k = 0; k < 3; ++k) {
+            rec[i].dir[k] = in[i].dir[k];
+            rec[i].color[k] = in[i].color[k];
+            rec[i].pos[k] = in[i].pos[k];
+            ext[i * LIGHT_EXT + k] = in[i].axis[k];
+        }
+        ext[i * LIGHT_EXT + 3] = in[i].cos_inner;
+        ext[i * LIGHT_EXT + 4] = in[i].cos_outer;
+        ext[i * LIGHT_EXT + 5] = in[i].intensity;
+    }
+}
+
 struct SceneView {
     const RT_RO srt_collider* col;
     const RT_RO srt_material* mat;
     const RT_RO srt_texture* tex;
     const RT_RO uint8_t* texels;
-    const RT_RO srt_light* lights;
+    const RT_RO DevLight* lights;  // nlights records, then the lights' extension rows (DevLight above)
     const RT_RO double* media;
     const RT_RO double* glossy_f0;
     const RT_RO double* light_local;
@@ -1109,16 +1145,28 @@ RT_HD Child mkchild(d3 o, d3 d, d3 w, uint32_t medium, uint32_t dfl, uint32_t sl
     return c;
 }
 
-// min over the shadowed colliders of the distance along the light direction (glossy.py:53-59)
-// `stop`: the caller only asks whether the result is >= stop (seelight), so the BVH pass may stop
-// at the first shadowing triangle closer than that
+// shadow_nearest: min over the shadowed colliders of the distance along the light direction
+// (glossy.py:53-59).  `stop`: the caller only asks whether the result is >= stop (seelight), so the BVH
+// pass may stop at the first shadowing triangle closer than that
+//
+// A cuboid in the shadow test of light `light`: a light at infinity has its direction in the box frame
+// in light_local; the per-hit direction of a positional light (MAT_PLIGHT, passed as light < 0) is
+// rotated as any ray's (cuboid.py:105-140 with array D)
+template <uint32_t FEAT>
+RT_HD double shadow_cuboid_hit(const SceneView& S, const RT_RO srt_collider& cc, int c, int light, d3 O, d3 L, double& o) {
+    if constexpr ((FEAT & MAT_PLIGHT) != 0) {
+        if (light < 0) return cuboid_hit(cc.p, O, L, o);
+    }
+    return cuboid_hit_local(cc.p, O, ld3(S.light_local + ((int64_t)light * S.ncol + c) * 3), o);
+}
+
 // One collider of the shadow test (glossy.py:53-59) of a collider sequence, as shadow_nearest's loop
 template <uint32_t FEAT, int TYPE>
 RT_HD void shadow_step(const SceneView& S, const RT_RO srt_collider& cc, int c, int light, d3 O, d3 L, double& best,
                        bool& first) {
     if (!(cc.flags & SRT_CF_SHADOW)) return;
     double o, t;
-    if constexpr (TYPE == SRT_CUBOID) t = cuboid_hit_local(cc.p, O, ld3(S.light_local + ((int64_t)light * S.ncol + c) * 3), o);
+    if constexpr (TYPE == SRT_CUBOID) t = shadow_cuboid_hit<FEAT>(S, cc, c, light, O, L, o);
     else if constexpr (TYPE == SRT_SPHERE) t = sphere_hit(cc.p, O, L, o);
     else if constexpr (TYPE == SRT_PLANE) t = plane_hit(cc.p, O, L, o);
     else t = triangle_hit(cc.p, O, L, o);
@@ -1146,7 +1194,7 @@ RT_HD double shadow_nearest(const SceneView& S, int light, d3 O, d3 L, double st
             if (!(cc.flags & SRT_CF_SHADOW)) continue;
             double o, t;
             if (cc.type == SRT_CUBOID)
-                t = cuboid_hit_local(cc.p, O, ld3(S.light_local + ((int64_t)light * S.ncol + c) * 3), o);
+                t = shadow_cuboid_hit<FEAT>(S, cc, c, light, O, L, o);
             else
                 t = collider_hit<FEAT>(cc, O, L, o);
             best = first ? t : np_min(best, t);
@@ -1172,11 +1220,33 @@ RT_HD d3 hitin_albedo(const HitIn* hi) {
     return d3{hi->albedo[hi->pix], hi->albedo[hi->n + hi->pix], hi->albedo[2 * hi->n + hi->pix]};
 }
 
+// PositionalLight.get_distance / get_L at the hit point P (lights.py): d = pos - P, dist = sqrt(d.d),
+// L = d * (1.0 / dist)
+RT_HD void plight_at(const RT_RO DevLight& Lt, d3 P, d3& L, double& dist) {
+    const d3 d = sub(ld3(Lt.pos), P);
+    dist = sqrt(dot(d, d));
+    L = mul(d, 1.0 / dist);
+}
+// PositionalLight.get_irradiance: color * NdotL / dist**2.0 * intensity; a SpotLight's times its cone
+// factor s*s*(3 - 2*s), s = clip(((-L).axis - cos_outer) / (cos_inner - cos_outer), 0, 1)
+// (`x`: the light's extension row, SceneView::lights: axis 0-2, cos_inner 3, cos_outer 4, intensity 5)
+RT_HD d3 plight_irradiance(const RT_RO DevLight& Lt, const RT_RO double* x, d3 L, double dist, double NdotL) {
+    const Quot q(dist * dist);
+    d3 lv = mul(d3{q(Lt.color[0] * NdotL), q(Lt.color[1] * NdotL), q(Lt.color[2] * NdotL)}, x[5]);
+    if (Lt.flags & SRT_LF_SPOT) {
+        const double cs = dot(mul(L, -1.0), ld3(x));
+        const double s = np_clip((cs - x[4]) / (x[3] - x[4]), 0.0, 1.0);
+        lv = mul(lv, (s * s) * (3.0 - 2.0 * s));
+    }
+    return lv;
+}
+
 // Glossy.get_color (glossy.py:25-110)
 template <uint32_t FEAT = MAT_GENERIC | MAT_BVH, class E>
 RT_HD void shade_glossy(const SceneView& S, const RT_RO srt_collider& c, int mi, const Ray& r, double t, double orient,
                         E& em, uint32_t& err, const HitIn* hi = nullptr) {
     constexpr bool HITIN = (FEAT & MAT_HITIN) != 0;
+    constexpr bool PLIGHT = (FEAT & MAT_PLIGHT) != 0;
     const RT_RO srt_material& m = S.mat[mi];
     RT_T0(tg0);
     d3 P = add(r.o, mul(r.d, t));
@@ -1199,7 +1269,7 @@ RT_HD void shade_glossy(const SceneView& S, const RT_RO srt_collider& c, int mi,
     uint32_t see = 0u;
     [[maybe_unused]] int uk0 = 0;  // (MAT_HITIN) user lights met so far
     for (int l = 0; l < S.nlights && l < 32; ++l) {
-        const RT_RO srt_light& Lt = S.lights[l];
+        const RT_RO DevLight& Lt = S.lights[l];
         if constexpr (HITIN) {
             // a user Light: seelight = light_nearest >= get_distance(hit.point) (glossy.py:57)
             if (Lt.type == SRT_LIGHT_USER) {
@@ -1207,6 +1277,22 @@ RT_HD void shade_glossy(const SceneView& S, const RT_RO srt_collider& c, int mi,
                 ++uk0;
                 if (S.nshadow > 0) {
                     if (shadow_nearest<FEAT>(S, l, nudged, ld3(Lt.dir), stop) >= stop) see |= 1u << l;
+                    em.shadow(1);
+                } else {
+                    see |= 1u << l;
+                }
+                continue;
+            }
+        }
+        if constexpr (PLIGHT) {
+            // a positional light: the shadow ray runs along the hit's own L and stops at the light
+            // (seelight = light_nearest >= dist: an occluder beyond the light does not shadow)
+            if (Lt.type == SRT_LIGHT_POSITIONAL) {
+                if (S.nshadow > 0) {
+                    d3 Lp;
+                    double dp;
+                    plight_at(Lt, P, Lp, dp);
+                    if (shadow_nearest<FEAT>(S, -1, nudged, Lp, dp) >= dp) see |= 1u << l;
                     em.shadow(1);
                 } else {
                     see |= 1u << l;
@@ -1236,19 +1322,29 @@ RT_HD void shade_glossy(const SceneView& S, const RT_RO srt_collider& c, int mi,
     d3 color = mul(ld3(S.ambient), diff);
     [[maybe_unused]] int uk = 0;
     for (int l = 0; l < S.nlights; ++l) {
-        const RT_RO srt_light& Lt = S.lights[l];
+        const RT_RO DevLight& Lt = S.lights[l];
         bool user = false;
         if constexpr (HITIN) user = Lt.type == SRT_LIGHT_USER;
-        if (Lt.type != SRT_LIGHT_DIRECTIONAL && !user) {
+        [[maybe_unused]] bool plight = false;
+        if constexpr (PLIGHT) plight = Lt.type == SRT_LIGHT_POSITIONAL;
+        if (Lt.type != SRT_LIGHT_DIRECTIONAL && !user && !plight) {
             // PointLight.get_L reads the undefined names M and dist_light (lights.py:30-31): the
             // reference's render raises NameError at the first Glossy hit, so does this one
             err |= ERR_NAME;
             continue;
         }
-        const d3 L = ld3(Lt.dir);
+        d3 L = ld3(Lt.dir);
         double dist = SKYBOX_DISTANCE;
         double NdotL = np_max(dot(N, L), 0.0);
         d3 lv = mul(ld3(Lt.color), NdotL);
+        if constexpr (PLIGHT) {
+            if (plight) {  // get_distance, get_L, NdotL, get_irradiance at the un-nudged hit point (glossy.py:38-44)
+                plight_at(Lt, P, L, dist);
+                NdotL = np_max(dot(N, L), 0.0);
+                const RT_RO double* ext = reinterpret_cast<const RT_RO double*>(S.lights + S.nlights);
+                lv = plight_irradiance(Lt, ext + (int64_t)l * LIGHT_EXT, L, dist, NdotL);
+            }
+        }
         if constexpr (HITIN) {
             if (user) {  // get_distance(hit.point), get_irradiance(dist_light, NdotL) as the user's code gave them
                 dist = hi->ldist[(int64_t)uk * hi->n + hi->pix];
@@ -1263,7 +1359,7 @@ RT_HD void shade_glossy(const SceneView& S, const RT_RO srt_collider& c, int mi,
             seelight = ((see >> l) & 1u) ? 1.0 : 0.0;
 #ifndef RT_ABL_SHADOW
         } else if (S.nshadow > 0) {
-            double ln = shadow_nearest<FEAT>(S, l, nudged, L, dist);
+            double ln = shadow_nearest<FEAT>(S, plight ? -1 : l, nudged, L, dist);
             seelight = (ln >= dist) ? 1.0 : 0.0;
             em.shadow(1);
 #endif

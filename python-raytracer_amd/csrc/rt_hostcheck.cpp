@@ -29,6 +29,8 @@ struct Scene {
 thread_local BvhBuild g_bvh;  // the BVH of the scene of the current call
 thread_local int g_use_bvh = 1;
 thread_local bool g_vattr = false;  // the scene of the current call has SRT_CF_VNORMAL / SRT_CF_VUV triangles
+thread_local bool g_plight = false;  // ... has an SRT_LIGHT_POSITIONAL light
+thread_local std::vector<srt_light> g_lights;  // its light table as the kernels read it (pack_lights)
 // rows of the current hc_render (null: identity / hc_trace): Monte-Carlo draws are keyed by the
 // global pixel, as key_pix in rt_kernels.hip
 thread_local const int32_t* g_rows = nullptr;
@@ -55,7 +57,9 @@ SceneView view_of(const srt_scene_desc* d) {
     S.bvh_nodes = (int)g_bvh.nodes.size();
     S.bvh_bound = g_bvh.bound;
     S.col = d->colliders; S.mat = d->materials; S.tex = d->textures; S.texels = d->texels;
-    S.lights = d->lights; S.media = d->media; S.glossy_f0 = d->glossy_f0; S.light_local = d->light_local;
+    g_lights.assign((size_t)(d->n_lights > 0 ? d->n_lights : 0), srt_light{});  // (the kernels' layout, as the upload's)
+    if (d->n_lights > 0) pack_lights(d->lights, d->n_lights, g_lights.data());
+    S.lights = reinterpret_cast<const DevLight*>(g_lights.data()); S.media = d->media; S.glossy_f0 = d->glossy_f0; S.light_local = d->light_local;
     S.importance = d->importance;
     S.ncol = d->n_colliders; S.nmat = d->n_materials; S.ntex = d->n_textures; S.nlights = d->n_lights;
     S.nmedia = d->n_media; S.nimp = d->n_importance;
@@ -68,6 +72,9 @@ SceneView view_of(const srt_scene_desc* d) {
         if (d->colliders[i].type == SRT_TRIANGLE && (d->colliders[i].flags & (SRT_CF_VNORMAL | SRT_CF_VUV)))
             g_vattr = true;
     }
+    g_plight = false;  // (as the scan sets MAT_PLIGHT)
+    for (int i = 0; i < d->n_lights; ++i)
+        if (d->lights[i].type == SRT_LIGHT_POSITIONAL) g_plight = true;
     for (int k = 0; k < 3; ++k) S.ambient[k] = d->ambient[k];
     return S;
 }
@@ -148,7 +155,9 @@ void trace_one_feat(const SceneView& S, const Ray& r, int depth, uint64_t seed, 
 
 void trace_one(const SceneView& S, const Ray& r, int depth, uint64_t seed, std::vector<Ray>& next, double* fb,
                int64_t npix, uint32_t& err, int64_t& shadow, int32_t* hit_slot) {
-    if (g_vattr)
+    if (g_plight)  // (never with g_vattr: refused at lowering, as srt_upload_scene refuses it)
+        trace_one_feat<MAT_GENERIC | MAT_BVH | MAT_PLIGHT>(S, r, depth, seed, next, fb, npix, err, shadow, hit_slot);
+    else if (g_vattr)
         trace_one_feat<MAT_GENERIC | MAT_BVH | MAT_VATTR>(S, r, depth, seed, next, fb, npix, err, shadow, hit_slot);
     else
         trace_one_feat<MAT_GENERIC | MAT_BVH>(S, r, depth, seed, next, fb, npix, err, shadow, hit_slot);

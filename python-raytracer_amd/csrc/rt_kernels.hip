@@ -1230,6 +1230,9 @@ constexpr uint32_t LDS_STK = RT_BVH_LDS_STACK ? MAT_LDS_STACK : 0u, LDS_STK_FRAM
 constexpr uint32_t MATS_MESH = MATS_GLOSSY_SKY | MAT_TRI | MAT_BVH;  // a glossy TriangleMesh in the ex1 setting
 constexpr uint32_t MATS_MESH_VATTR = MATS_MESH | MAT_VATTR;                // ... smooth-shaded / textured
 constexpr uint32_t MATS_BVH_VATTR = MAT_GENERIC | MAT_BVH | MAT_VATTR;
+constexpr uint32_t MATS_GLOSSY_PLIGHT = MATS_GLOSSY_SKY | MAT_PLIGHT;  // positional lights (MAT_PLIGHT)
+constexpr uint32_t MATS_GENERIC_PLIGHT = MAT_GENERIC | MAT_PLIGHT;
+constexpr uint32_t MATS_BVH_PLIGHT = MAT_GENERIC | MAT_BVH | MAT_PLIGHT;
 const Variant VARIANTS[] = {
     {MATS_GLOSSY_SKY, k_primary<MATS_GLOSSY_SKY, OCC>, k_trace<MATS_GLOSSY_SKY, OCC>, k_frame<MATS_GLOSSY_SKY, OCC>, k_trace<MATS_GLOSSY_SKY, OCC, true>,
      k_primary<MATS_GLOSSY_SKY, RT_FUSE_OCC, true>, k_primary_lean<MATS_GLOSSY_SKY, RT_FUSE_OCC>,
@@ -1255,6 +1258,19 @@ const Variant VARIANTS[] = {
      k_frame<MAT_GENERIC | MAT_VATTR, OCC>, k_trace<MAT_GENERIC | MAT_VATTR, OCC, true>},
     {MATS_BVH_VATTR, k_primary<MATS_BVH_VATTR | LDS_STK, OCC>, k_trace<MATS_BVH_VATTR | LDS_STK, OCC>,
      k_frame<MATS_BVH_VATTR | LDS_STK_FRAME, OCC>, k_trace<MATS_BVH_VATTR | LDS_STK, OCC, true>},
+    // Scenes with a PositionalLight / SpotLight (MAT_PLIGHT, set by no scene without one, so these stay
+    // behind every variant above): Glossy surfaces under the sky box with the fused paths (a lit room
+    // on a large frame), then the generic rows with and without the BVH.  No collider-sequence variant
+    // carries the bit: such a scene intersects its colliders in the loop.  Nor does a MAT_VATTR one: a
+    // scene with both is refused at upload (check_scene_desc; the two rows cost more build time than
+    // their share of the kernels).
+    {MATS_GLOSSY_PLIGHT, k_primary<MATS_GLOSSY_PLIGHT, OCC>, k_trace<MATS_GLOSSY_PLIGHT, OCC>,
+     k_frame<MATS_GLOSSY_PLIGHT, OCC>, k_trace<MATS_GLOSSY_PLIGHT, OCC, true>,
+     k_primary<MATS_GLOSSY_PLIGHT, RT_FUSE_OCC, true>},
+    {MATS_GENERIC_PLIGHT, k_primary<MATS_GENERIC_PLIGHT, OCC>, k_trace<MATS_GENERIC_PLIGHT, OCC>,
+     k_frame<MATS_GENERIC_PLIGHT, OCC>, k_trace<MATS_GENERIC_PLIGHT, OCC, true>},
+    {MATS_BVH_PLIGHT, k_primary<MATS_BVH_PLIGHT | LDS_STK, OCC>, k_trace<MATS_BVH_PLIGHT | LDS_STK, OCC>,
+     k_frame<MATS_BVH_PLIGHT | LDS_STK_FRAME, OCC>, k_trace<MATS_BVH_PLIGHT | LDS_STK, OCC, true>},
 #endif
 };
 // Variants for scenes of a given collider sequence (rt_device.h seq_of: the colliders intersected in
@@ -2789,8 +2805,24 @@ static int check_scene_desc(const srt_scene_desc* d) {
             return fail(SRT_ERR_ARG, "SRT_MF_HIT_ALBEDO: a Glossy / Diffuse / Emissive material with tex = -1");
     }
     for (int i = 0; i < d->n_lights; ++i)
-        if (d->lights[i].type < SRT_LIGHT_DIRECTIONAL || d->lights[i].type > SRT_LIGHT_USER)
+        if (d->lights[i].type < SRT_LIGHT_DIRECTIONAL || d->lights[i].type > SRT_LIGHT_POSITIONAL)
             return fail(SRT_ERR_ARG, "bad light type");
+    // the per-hit-input shaders (srt_shade_level_inputs) have no positional-light instantiation
+    bool positional = false, inputs = false;
+    for (int i = 0; i < d->n_lights; ++i) {
+        positional |= d->lights[i].type == SRT_LIGHT_POSITIONAL;
+        inputs |= d->lights[i].type == SRT_LIGHT_USER;
+    }
+    for (int i = 0; i < d->n_materials; ++i) inputs |= (d->materials[i].flags & SRT_MF_HIT_ALBEDO) != 0;
+    if (positional && inputs)
+        return fail(SRT_ERR_ARG, "an SRT_LIGHT_POSITIONAL light in a scene shaded with per-hit inputs "
+                                 "(SRT_MF_HIT_ALBEDO material or SRT_LIGHT_USER light) is not supported");
+    // ... and no kernel variant holds both the positional lights and the per-vertex triangle attributes
+    if (positional)
+        for (int i = 0; i < d->n_colliders; ++i)
+            if (d->colliders[i].type == SRT_TRIANGLE && (d->colliders[i].flags & (SRT_CF_VNORMAL | SRT_CF_VUV)))
+                return fail(SRT_ERR_ARG, "an SRT_LIGHT_POSITIONAL light in a scene with SRT_CF_VNORMAL / SRT_CF_VUV "
+                                         "triangles (a smooth or textured mesh) is not supported");
     return SRT_OK;
 }
 
@@ -2904,7 +2936,11 @@ static int upload_tables(srt_ctx* c, const srt_scene_desc* d, SceneView& S, bool
     const TexelPool tp = plan_texel_pool(d, d->texel_bytes > 0 && d->texels && !is_device_ptr(d->texels));
     if ((rc = upload(c, tp.tex.data(), d->n_textures, &tex))) return rc;
     if ((rc = upload_texel_pool(c, d, tp))) return rc;
-    if ((rc = upload(c, d->lights, d->n_lights, &lights))) return rc;
+    // the light table in the kernels' layout (rt_device.h DevLight: the common fields, then the
+    // positional lights' extension rows; the table's bytes in all)
+    std::vector<srt_light> packed((size_t)std::max(0, d->n_lights));
+    if (d->n_lights > 0) pack_lights(d->lights, d->n_lights, packed.data());
+    if ((rc = upload(c, packed.data(), d->n_lights, &lights))) return rc;
     if ((rc = upload(c, d->media, (int64_t)d->n_media * 6, &media))) return rc;
     if ((rc = upload(c, d->glossy_f0, (int64_t)d->n_materials * d->n_media * 3, &f0))) return rc;
     if ((rc = upload(c, d->light_local, (int64_t)d->n_lights * d->n_colliders * 3, &ll))) return rc;
@@ -2968,6 +3004,8 @@ static void derive_scene_facts(srt_ctx* c, const srt_scene_desc* d, const SceneV
     for (int i = 0; i < d->n_colliders; ++i)
         if (d->colliders[i].type == SRT_TRIANGLE && (d->colliders[i].flags & (SRT_CF_VNORMAL | SRT_CF_VUV)))
             c->mats |= MAT_VATTR;
+    for (int i = 0; i < d->n_lights; ++i)
+        if (d->lights[i].type == SRT_LIGHT_POSITIONAL) c->mats |= MAT_PLIGHT;
     c->seq = 0;
     if (S.bvh_nodes == 0 && d->n_colliders <= SEQ_MAX) {
         int types[SEQ_MAX];
@@ -3121,6 +3159,9 @@ int trace_impl(srt_ctx* c, const srt_trace_args* a, const int32_t* fid, const do
                                           : (bvh ? k_shade_forced_inputs<MAT_GENERIC | MAT_BVH | MAT_HITIN>
                                                  : k_shade_forced_inputs<MAT_GENERIC | MAT_HITIN>),
                                        dim3(trace_grid(c)), dim3(BLOCK), lut_bytes(c), c->f->stream, P, H);
+                } else if (c->mats & MAT_PLIGHT) {  // (never with MAT_VATTR: check_scene_desc)
+                    hipLaunchKernelGGL(bvh ? k_shade_forced<MATS_BVH_PLIGHT> : k_shade_forced<MATS_GENERIC_PLIGHT>,
+                                       dim3(trace_grid(c)), dim3(BLOCK), lut_bytes(c), c->f->stream, P);
                 } else {
                     hipLaunchKernelGGL(va ? (bvh ? k_shade_forced<MATS_BVH_VATTR> : k_shade_forced<MAT_GENERIC | MAT_VATTR>)
                                           : (bvh ? k_shade_forced<MAT_GENERIC | MAT_BVH> : k_shade_forced<MAT_GENERIC>),

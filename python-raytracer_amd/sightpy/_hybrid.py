@@ -26,7 +26,10 @@ step the device can take on the device:
     maximum(N.dot(L), 0)` of the material's device normal (glossy.py:41; that dot product is the
     callback's argument, nothing else of the material is computed on the host).  Their values go to
     the device per hit.  `get_L()` must be one direction (a vec3 of scalars): a per-ray light
-    direction is refused.  Per-hit inputs exist only in this host-driven path.
+    direction is refused.  Per-hit inputs exist only in this host-driven path.  (The built-in
+    `PositionalLight` / `SpotLight` need none of this: the device computes their direction, distance
+    and irradiance per hit, also in a scene with user colliders or materials; beside a user texture or
+    user Light they are refused, `_check`.)
 
 Scenes made only of built-in classes never come here: they render in the device kernels whole.
 
@@ -99,11 +102,11 @@ _LIGHT_METHODS = ("get_L", "get_distance", "get_irradiance")
 
 
 def device_light(l):
-    """A `DirectionalLight` or `PointLight` (or a subclass of one that keeps get_L / get_distance /
-    get_irradiance): a record of the device's light table."""
-    from .lights import DirectionalLight, PointLight
+    """A `DirectionalLight`, `PointLight`, `PositionalLight` or `SpotLight` (or a subclass of one that
+    keeps get_L / get_distance / get_irradiance): a record of the device's light table."""
+    from .lights import DirectionalLight, PointLight, PositionalLight, SpotLight
 
-    for base in (DirectionalLight, PointLight):
+    for base in (DirectionalLight, PointLight, SpotLight, PositionalLight):  # (a SpotLight is a PositionalLight)
         if isinstance(l, base):
             t = type(l)
             return all(getattr(t, m, None) is getattr(base, m, None) for m in _LIGHT_METHODS)
@@ -156,6 +159,12 @@ def is_hybrid(scene):
 
 def _check(scene):
     from .materials import Glossy
+    from .lights import PositionalLight
+
+    if needs_inputs(scene) and any(isinstance(l, PositionalLight) and device_light(l) for l in scene.Light_list):
+        raise NotImplementedError(
+            "a PositionalLight / SpotLight in a scene that needs per-hit inputs (a user texture on a built-in "
+            "material, or a user Light): the per-hit-input shaders have no positional-light path")
 
     for c in scene.collider_list:
         m = c.assigned_primitive.material

@@ -32,7 +32,7 @@ from .materials.diffuse import Diffuse
 from .materials.emissive import Emissive
 from .textures.texture import image, solid_color
 from .backgrounds.skybox import SkyBox_Material
-from .lights import DirectionalLight, PointLight
+from .lights import DirectionalLight, PointLight, PositionalLight, SpotLight
 
 _LIN_LUT = sRGB_to_sRGB_linear(np.arange(256) / 256.0)  # image textures (load_image_as_linear_sRGB)
 _RAW_LUT = np.arange(256) / 256.0                        # load_image (lightmap, tables, noise, normal maps)
@@ -55,7 +55,9 @@ class Lowered:
         self.materials = None
         self.textures = None
         self.texels = None
-        self.lights = None
+        self.lights = None      # the records' common part (N.LIGHT_BASE_DTYPE; `reserved` holds the SRT_LF_* flags)
+        self.light_ext = None   # (n, 6): axis, cos_inner, cos_outer, intensity (positional lights)
+        self._light_table = None
         self.media = None
         self.glossy_f0 = None
         self.light_local = None
@@ -68,8 +70,19 @@ class Lowered:
         self.texel_key = 0
         self.device_index = []  # scene.collider_list index -> device collider index (-1: a user class, _hybrid)
 
+    def light_table(self):
+        """The srt_light records (N.LIGHT_DTYPE) of `lights` and `light_ext`."""
+        t = np.zeros(len(self.lights), dtype=N.LIGHT_DTYPE)
+        for f in ("type", "dir", "color", "pos"):
+            t[f] = self.lights[f]
+        t["flags"] = self.lights["reserved"]
+        t["axis"] = self.light_ext[:, 0:3]
+        t["cos_inner"], t["cos_outer"], t["intensity"] = self.light_ext[:, 3], self.light_ext[:, 4], self.light_ext[:, 5]
+        return t
+
     def desc(self):
         d = N.SceneDesc()
+        self._light_table = self.light_table()  # (kept alive with the other arrays)
         d.n_colliders = len(self.colliders)
         d.n_materials = len(self.materials)
         d.n_textures = len(self.textures)
@@ -81,7 +94,7 @@ class Lowered:
         d.textures = N.ptr(self.textures) if len(self.textures) else None
         d.texels = N.ptr(self.texels) if self.texels.size else None
         d.texel_bytes = int(self.texels.size)
-        d.lights = N.ptr(self.lights) if len(self.lights) else None
+        d.lights = N.ptr(self._light_table) if len(self.lights) else None
         d.media = N.ptr(self.media)
         d.glossy_f0 = N.ptr(self.glossy_f0) if self.glossy_f0.size else None
         d.light_local = N.ptr(self.light_local) if self.light_local.size else None
@@ -94,7 +107,7 @@ class Lowered:
 
     def signature(self):
         parts = [self.colliders.tobytes(), self.materials.tobytes(), self.textures.tobytes(),
-                 self.lights.tobytes(), self.media.tobytes(), self.glossy_f0.tobytes(),
+                 self.lights.tobytes(), self.light_ext.tobytes(), self.media.tobytes(), self.glossy_f0.tobytes(),
                  self.light_local.tobytes(), self.importance.tobytes(), repr(self.ambient).encode(),
                  str(self.max_ray_depth).encode()]
         return hash((tuple(parts), self.texels.size, self.texel_key))
@@ -514,7 +527,8 @@ def lower_scene(scene, extra_media=()):
     L.max_ray_depth = int(max([int(c.assigned_primitive.max_ray_depth) for c in colliders], default=0))
 
     # ---- lights -----------------------------------------------------------------------------
-    lrecs = np.zeros(len(scene.Light_list), dtype=N.LIGHT_DTYPE)
+    lrecs = np.zeros(len(scene.Light_list), dtype=N.LIGHT_BASE_DTYPE)
+    lext = np.zeros((len(scene.Light_list), N.LIGHT_EXT))
     light_local = np.zeros((len(scene.Light_list), len(colliders), 3))
     for i, lt in enumerate(scene.Light_list):
         if isinstance(lt, DirectionalLight) and device_light(lt):
@@ -529,6 +543,22 @@ def lower_scene(scene, extra_media=()):
             lrecs[i]["type"] = N.LIGHT_POINT
             lrecs[i]["pos"] = _f3(lt.pos)
             lrecs[i]["color"] = _f3(lt.color)
+        elif isinstance(lt, PositionalLight) and device_light(lt):
+            # direction, distance and irradiance per hit on the device (shade_glossy, MAT_PLIGHT); its
+            # light_local rows stay zero: a cuboid rotates the per-hit direction itself
+            lrecs[i]["type"] = N.LIGHT_POSITIONAL
+            lrecs[i]["pos"] = _f3(lt.pos)
+            lrecs[i]["color"] = _f3(lt.color)
+            lext[i, 5] = float(lt.intensity)
+            if isinstance(lt, SpotLight):
+                lrecs[i]["reserved"] = N.LF_SPOT
+                lext[i, 0:3] = _f3(lt.axis)
+                lext[i, 3], lext[i, 4] = lt.cos_inner, lt.cos_outer
+        elif isinstance(lt, PositionalLight):
+            raise NotImplementedError(
+                "light %s overrides a method of %s: its get_L(M) is a direction per hit; a per-ray light direction "
+                "of a user Light is not supported" % (type(lt).__name__, "SpotLight" if isinstance(lt, SpotLight)
+                                                      else "PositionalLight"))
         else:
             # a user Light subclass: one direction for every hit; its get_distance / get_irradiance
             # run on the host and arrive per hit (srt_shade_level_inputs)
@@ -542,7 +572,12 @@ def lower_scene(scene, extra_media=()):
             for j, c in enumerate(colliders):
                 if isinstance(c, Cuboid_Collider):
                     light_local[i, j] = _f3(Ld.matmul(c.basis_matrix))
+    if (lrecs["type"] == N.LIGHT_POSITIONAL).any() and (crecs["flags"] & (N.CF_VNORMAL | N.CF_VUV)).any():
+        raise NotImplementedError(
+            "a PositionalLight / SpotLight in a scene with a smooth or textured TriangleMesh (per-vertex normals "
+            "or texture coordinates): no kernel variant holds both")
     L.lights = lrecs
+    L.light_ext = lext
     L.light_local = np.ascontiguousarray(light_local)
 
     imp = np.zeros((len(scene.importance_sampled_list), 4))

@@ -26,7 +26,8 @@ GLOSSY, REFRACTIVE, THINFILM, DIFFUSE, EMISSIVE, SKY = 0, 1, 2, 3, 4, 5
 CF_SHADOW, CF_MC, CF_UV_CROSS = 1, 2, 4
 CF_VNORMAL, CF_VUV = 8, 16  # Triangle: per-vertex normals / texture coordinates in the record
 MF_ROUGH, MF_LIGHTMAP, MF_NOISE, MF_HIT_ALBEDO = 1, 2, 4, 8
-LIGHT_DIRECTIONAL, LIGHT_POINT, LIGHT_USER = 0, 1, 2
+LIGHT_DIRECTIONAL, LIGHT_POINT, LIGHT_USER, LIGHT_POSITIONAL = 0, 1, 2, 3
+LF_SPOT = 1
 
 ERR_ARG, ERR_HIP, ERR_NOSCENE, ERR_MEMORY, ERR_INDEX, ERR_DEPTH, ERR_NAME = -1, -2, -3, -4, -5, -6, -7
 
@@ -71,11 +72,22 @@ TEXTURE_DTYPE = np.dtype(
     align=True,
 )
 LIGHT_DTYPE = np.dtype(
+    [("type", "<i4"), ("flags", "<u4"), ("dir", "<f8", (3,)), ("color", "<f8", (3,)), ("pos", "<f8", (3,)),
+     ("axis", "<f8", (3,)), ("cos_inner", "<f8"), ("cos_outer", "<f8"), ("intensity", "<f8")],
+    align=True,
+)
+# The part of a light record every light has (srt_light's first 80 bytes: its layout before ABI 7, when
+# the flags word was still `reserved`): what `Lowered.lights` holds, beside the rows of the fields
+# appended since (`Lowered.light_ext`: axis, cos_inner, cos_outer, intensity) -- the two parts the
+# device keeps the table in (csrc/rt_device.h DevLight).  `Lowered.light_table()` joins them.
+LIGHT_BASE_DTYPE = np.dtype(
     [("type", "<i4"), ("reserved", "<i4"), ("dir", "<f8", (3,)), ("color", "<f8", (3,)), ("pos", "<f8", (3,))],
     align=True,
 )
+LIGHT_EXT = 6
+assert LIGHT_BASE_DTYPE.itemsize == 80 and LIGHT_BASE_DTYPE.itemsize + 8 * LIGHT_EXT == LIGHT_DTYPE.itemsize
 assert COLLIDER_DTYPE.itemsize == 416 and MATERIAL_DTYPE.itemsize == 160
-assert TEXTURE_DTYPE.itemsize == 2088 and LIGHT_DTYPE.itemsize == 80
+assert TEXTURE_DTYPE.itemsize == 2088 and LIGHT_DTYPE.itemsize == 128
 
 _p = ctypes.c_void_p
 _d3 = ctypes.c_double * 3
@@ -236,7 +248,7 @@ class HitInputs(ctypes.Structure):
 
 # name -> (restype, argtypes) for every entry point of include/sightpy_rt.h
 RENDER_ASYNC, RENDER_SHARDED, RENDER_GATHER_RGB, RENDER_RGB_ROWS, RENDER_RGB_LOCAL, RENDER_RGBX = 1, 2, 4, 8, 16, 32  # SRT_RENDER_*
-ABI_VERSION = 6  # SRT_ABI_VERSION of include/sightpy_rt.h
+ABI_VERSION = 7  # SRT_ABI_VERSION of include/sightpy_rt.h
 COMM_ID_BYTES = 128
 
 SIGNATURES = {

@@ -38,6 +38,12 @@ class Scene:
     def add_PointLight(self, pos, color):
         self.Light_list += [lights.PointLight(pos, color)]
 
+    def add_PositionalLight(self, pos, color, intensity=100.0):
+        self.Light_list += [lights.PositionalLight(pos, color, intensity)]
+
+    def add_SpotLight(self, pos, direction, color, inner_deg, outer_deg, intensity=100.0):
+        self.Light_list += [lights.SpotLight(pos, direction, color, inner_deg, outer_deg, intensity)]
+
     def add_DirectionalLight(self, Ldir, color):
         self.Light_list += [lights.DirectionalLight(Ldir.normalize(), color)]
 
