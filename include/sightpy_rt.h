@@ -29,6 +29,8 @@
  *   srt_texture_lookup     <- image.get_color(hit)     sightpy/textures/texture.py:32-39
  *   srt_material_normal    <- Material.get_Normal(hit) sightpy/materials/material.py:18-36
  *   srt_primary_rays       <- Camera.get_ray(n)       sightpy/camera.py:51-85
+ *   srt_render_aovs, srt_denoise: no counterpart (first-hit guide images and the a-trous filter that
+ *                             denoises a low-sample frame with them)
  *   srt_upload_scene       <- (scene lowering; the reference deep-copies the Scene per task,
  *                              scene.py:85)
  *
@@ -442,6 +444,60 @@ int srt_material_normal(srt_ctx* ctx, const srt_collider* collider, const srt_te
                         int64_t n, double* N);
 int srt_primary_rays(srt_ctx* ctx, const srt_camera* cam, const double* jitter /* [4][n] */,
                      double* origin /* [3][n] */, double* dir /* [3][n] */);
+
+/* ---- denoising a Monte-Carlo frame (no reference counterpart; csrc/rt_denoise.h) ----------------
+ * srt_render_aovs: the first-hit guide images of the resident scene, one pixel-centre pinhole ray per
+ * pixel (srt_primary_rays' ray for the jitter (0.5, 0.5, 0, 0)), n = width * height, planar.  Any
+ * output pointer may be NULL.  A miss and a hit on the SkyBox / Panorama collider are background:
+ * normal, albedo and position (0, 0, 0), hit_id and depth as found.  An exactly zero normal marks the
+ * background (normals of real hits have unit length).
+ * SRT_ERR_NOSCENE without a scene; SRT_ERR_ARG when the scene holds an SRT_MF_HIT_ALBEDO material
+ * (its albedo is the value of the user's Python). */
+typedef struct srt_aov_out {
+    int32_t* hit_id;  /* [n] nearest collider, -1 = miss (as srt_render_args.out_hit_id) */
+    double* depth;    /* [n] distance t, 1e39 (FARAWAY) for a miss */
+    double* position; /* [3][n] O + D * t, the un-nudged hit point */
+    double* normal;   /* [3][n] Collider.get_Normal * orientation (vertex normals interpolated on
+                         SRT_CF_VNORMAL triangles; normal maps are not applied) */
+    double* albedo;   /* [3][n] Glossy: the diffuse term (solid colour, or texel * diff_coeff);
+                         Diffuse / Emissive: the solid colour or the texel; Refractive / ThinFilm: 1 */
+    double ms_kernel; /* out: duration of the guide kernel, HIP events */
+} srt_aov_out;
+int srt_render_aovs(srt_ctx* ctx, const srt_camera* cam, srt_aov_out* out);
+
+/* srt_denoise: edge-avoiding a-trous wavelet filter of a linear-RGB frame, guided by normal, albedo,
+ * position and depth images (srt_render_aovs', or the caller's own).  Level l = 0 .. levels-1 filters
+ * colour c into c' with the 5x5 B3-spline taps h = (1/16, 1/4, 3/8, 1/4, 1/16) spread by s = 2^l:
+ *   q = p + s * (dx, dy), dy = -2..2 (outer), dx = -2..2 (inner), sigma_c(l) = sigma_color * 2^-l
+ *   w = h[dy+2] * h[dx+2] * exp(-(|c_p - c_q|^2 / sigma_c(l)^2 + |n_p - n_q|^2 / sigma_normal^2
+ *                                 + |a_p - a_q|^2 / sigma_albedo^2
+ *                                 + (|n_p . (x_q - x_p)| / t_p)^2 / sigma_plane^2))
+ *   w = 0 when q is outside the image, q is background (zero normal) or c_q is not finite; the centre
+ *   tap always weighs h[2] * h[2];  c'_p = sum(w * c_q) / sum(w), summed in tap order
+ * A background pixel and a pixel whose own colour is not finite are copied through; levels = 0 copies
+ * rgb through.  All float64.  Pointers may address host or device memory (device arrays are used in
+ * place).  Needs no scene.  SRT_ERR_ARG: a sigma <= 0, levels outside 0..8, a NULL input, a
+ * non-positive size, no output. */
+#define SRT_DENOISE_RGBX 2 /* out_srgb8 as 4-byte pixels (R, G, B, 255), as SRT_RENDER_RGBX */
+#define SRT_DENOISE_MAX_LEVELS 8
+typedef struct srt_denoise_args {
+    const double* rgb;      /* [3][n] linear RGB */
+    const double* normal;   /* [3][n] */
+    const double* albedo;   /* [3][n] */
+    const double* position; /* [3][n] */
+    const double* depth;    /* [n] */
+    int32_t levels;         /* 0..8 */
+    int32_t flags;          /* SRT_DENOISE_* */
+    double sigma_color;
+    double sigma_normal;
+    double sigma_albedo;
+    double sigma_plane;
+    double* out_rgb;        /* [3][n] filtered linear RGB, or NULL */
+    uint8_t* out_srgb8;     /* [n][3] ([n][4] with SRT_DENOISE_RGBX) resolved as srt_render resolves, or NULL */
+    double* ms_levels;      /* host [levels + 1]: duration of each level's kernel, then of the whole chain
+                               from the first launch to the end of the resolve (HIP events), or NULL */
+} srt_denoise_args;
+int srt_denoise(srt_ctx* ctx, int32_t width, int32_t height, const srt_denoise_args* args);
 /* numpy's legacy global-RNG stream on the device: writes the n_out doubles that
  * `np.random.rand(n_out)` would return for the RandomState with MT19937 key[624] and position
  * pos (0..624, as in np.random.get_state()), then consumes n_skip more draws, and returns the

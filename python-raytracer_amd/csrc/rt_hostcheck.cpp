@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "rt_bvh.h"
+#include "rt_denoise.h"
 #include "rt_device.h"
 #include "rt_mt.h"
 
@@ -336,6 +337,64 @@ int hc_primary_rays(const srt_camera* cam, const double* J, double* O, double* D
         O[i] = o.x; O[n + i] = o.y; O[2 * n + i] = o.z;
         D[i] = d.x; D[n + i] = d.y; D[2 * n + i] = d.z;
     }
+    return SRT_OK;
+}
+
+// k_aov: the first-hit guide images (rt_denoise.h aov_pixel), host pointers; any output may be NULL
+int hc_aovs(const srt_scene_desc* d, const srt_camera* cam, srt_aov_out* out) {
+    SceneView S = view_of(d);
+    const int64_t n = (int64_t)cam->width * cam->height;
+    uint32_t err = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t row = i / cam->width, col = i % cam->width;
+        const AovPixel r = aov_pixel(S, *cam, cam->xs[col], cam->ys[row], err);
+        if (out->hit_id) out->hit_id[i] = r.id;
+        if (out->depth) out->depth[i] = r.t;
+        if (out->position) { out->position[i] = r.P.x; out->position[n + i] = r.P.y; out->position[2 * n + i] = r.P.z; }
+        if (out->normal) { out->normal[i] = r.N.x; out->normal[n + i] = r.N.y; out->normal[2 * n + i] = r.N.z; }
+        if (out->albedo) { out->albedo[i] = r.A.x; out->albedo[n + i] = r.A.y; out->albedo[2 * n + i] = r.A.z; }
+    }
+    return err_code(err);
+}
+
+// srt_denoise: the levels of k_atrous one after the other over two colour buffers, then k_denoise_resolve
+int hc_denoise(int32_t width, int32_t height, const srt_denoise_args* a) {
+    if (width <= 0 || height <= 0 || !a->rgb || !a->normal || !a->albedo || !a->position || !a->depth ||
+        a->levels < 0 || a->levels > SRT_DENOISE_MAX_LEVELS || !(a->sigma_color > 0.0) || !(a->sigma_normal > 0.0) ||
+        !(a->sigma_albedo > 0.0) || !(a->sigma_plane > 0.0)) {
+        g_err = "hc_denoise: bad argument";
+        return SRT_ERR_ARG;
+    }
+    const int64_t n = (int64_t)width * height;
+    AtrousPlanes G{a->rgb, a->normal, a->albedo, a->position, a->depth, n, width};
+    std::vector<double> pong[2];
+    for (int l = 0; l < a->levels; ++l) {
+        AtrousLevel K{};
+        K.W = width, K.H = height, K.step = 1 << l;
+        const double sc = a->sigma_color * ldexp(1.0, -l);
+        K.sc2 = sc * sc;
+        K.sn2 = a->sigma_normal * a->sigma_normal;
+        K.sa2 = a->sigma_albedo * a->sigma_albedo;
+        K.sp2 = a->sigma_plane * a->sigma_plane;
+        std::vector<double>& o = pong[l & 1];
+        o.resize((size_t)(3 * n));
+        for (int32_t y = 0; y < height; ++y)
+            for (int32_t x = 0; x < width; ++x) {
+                const d3 c = atrous_pixel(G, K, x, y);
+                const int64_t ip = (int64_t)y * width + x;
+                o[(size_t)ip] = c.x; o[(size_t)(n + ip)] = c.y; o[(size_t)(2 * n + ip)] = c.z;
+            }
+        G.rgb = o.data();
+    }
+    const bool rgbx = (a->flags & SRT_DENOISE_RGBX) != 0;
+    if (a->out_srgb8)
+        for (int64_t i = 0; i < n; ++i) {
+            const uint32_t v = denoise_resolve(d3{G.rgb[i], G.rgb[n + i], G.rgb[2 * n + i]});
+            uint8_t* px = a->out_srgb8 + (rgbx ? 4 : 3) * i;
+            px[0] = (uint8_t)v; px[1] = (uint8_t)(v >> 8); px[2] = (uint8_t)(v >> 16);
+            if (rgbx) px[3] = 255;
+        }
+    if (a->out_rgb) std::memmove(a->out_rgb, G.rgb, (size_t)(3 * n) * sizeof(double));
     return SRT_OK;
 }
 

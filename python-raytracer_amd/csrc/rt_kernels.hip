@@ -42,6 +42,7 @@
 
 #include "rt_bvh.h"
 #include "rt_device.h"
+#include "rt_denoise.h"
 #include "rt_mt.h"
 #include "rt_mt_kernel.h"
 
@@ -3284,6 +3285,35 @@ int run_kernel(srt_ctx* c, int64_t n, const uint32_t* dflags, int* flag_rc, K ke
     *flag_rc = check_flags(flags);
     return SRT_OK;
 }
+
+// HIP events of one call, destroyed with it
+struct EventList {
+    std::vector<hipEvent_t> e;
+    ~EventList() {
+        for (hipEvent_t v : e) (void)hipEventDestroy(v);
+    }
+    hipError_t create(int n) {
+        for (int i = 0; i < n; ++i) {
+            hipEvent_t v;
+            if (hipError_t rc = hipEventCreate(&v); rc != hipSuccess) return rc;
+            e.push_back(v);
+        }
+        return hipSuccess;
+    }
+};
+
+// an input array of a call: device memory is used in place, host memory is copied into a buffer of `bufs`
+template <typename T>
+hipError_t stage_in(DevList& bufs, const T* src, int64_t count, const T** dst) {
+    if (is_device_ptr(src)) {
+        *dst = src;
+        return hipSuccess;
+    }
+    T* p = nullptr;
+    const hipError_t e = bufs.in(&p, src, count);
+    *dst = p;
+    return e;
+}
 }  // namespace
 
 extern "C" {
@@ -3493,6 +3523,125 @@ int srt_primary_rays(srt_ctx* c, const srt_camera* cam, const double* J, double*
     if (int rc = run_kernel(c, n, nullptr, nullptr, k_primary_rays, k, dJ, n, dO, dD)) return rc;
     HIP_TRY(bufs.copy(O, dO, 3 * n));
     HIP_TRY(bufs.copy(D, dD, 3 * n));
+    return SRT_OK;
+}
+
+// ---- denoising (rt_denoise.h) -----------------------------------------------------------------------
+int srt_render_aovs(srt_ctx* c, const srt_camera* cam, srt_aov_out* out) {
+    if (!c || !cam || !out) return fail(SRT_ERR_ARG, "null argument");
+    if (!c->has_scene) return fail(SRT_ERR_NOSCENE, "no scene uploaded");
+    if (cam->width <= 0 || cam->height <= 0 || !cam->xs || !cam->ys) return fail(SRT_ERR_ARG, "bad camera");
+    if (std::find(c->col_hit_albedo.begin(), c->col_hit_albedo.end(), 1) != c->col_hit_albedo.end())
+        return fail(SRT_ERR_ARG, "srt_render_aovs: the scene holds an SRT_MF_HIT_ALBEDO material (a user texture: "
+                                 "its albedo is not known to the device)");
+    HIP_TRY(hipSetDevice(c->device));
+    DevList bufs;
+    const int64_t n = (int64_t)cam->width * cam->height;
+    AovOut d{};
+    if (out->hit_id) HIP_TRY(bufs.alloc(&d.hit_id, n));
+    if (out->depth) HIP_TRY(bufs.alloc(&d.depth, n));
+    if (out->position) HIP_TRY(bufs.alloc(&d.position, 3 * n));
+    if (out->normal) HIP_TRY(bufs.alloc(&d.normal, 3 * n));
+    if (out->albedo) HIP_TRY(bufs.alloc(&d.albedo, 3 * n));
+    double *xs, *ys;
+    uint32_t* dflags;
+    HIP_TRY(bufs.in(&xs, cam->xs, cam->width));
+    HIP_TRY(bufs.in(&ys, cam->ys, cam->height));
+    HIP_TRY(bufs.alloc(&dflags, 1));
+    HIP_TRY(hipMemset(dflags, 0, 4));
+    srt_camera k = *cam;
+    k.xs = xs;
+    k.ys = ys;
+    SceneView S = c->S;
+    S.nlut_lds = 0;  // (k_aov stages no texture tables in LDS: it reads them from the texture records)
+    EventList ev;
+    HIP_TRY(ev.create(2));
+    hipStream_t st = c->f->stream;
+    HIP_TRY(hipEventRecord(ev.e[0], st));
+    hipLaunchKernelGGL(k_aov, dim3(grid_for(n, c->max_blocks)), dim3(DN_BLOCK), 0, st, S, k, d, dflags);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev.e[1], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+    out->ms_kernel = ms;
+    uint32_t flags = 0;
+    HIP_TRY(hipMemcpy(&flags, dflags, 4, hipMemcpyDefault));
+    if (int rc = check_flags(flags)) return rc;
+    if (out->hit_id) HIP_TRY(bufs.copy(out->hit_id, d.hit_id, n));
+    if (out->depth) HIP_TRY(bufs.copy(out->depth, d.depth, n));
+    if (out->position) HIP_TRY(bufs.copy(out->position, d.position, 3 * n));
+    if (out->normal) HIP_TRY(bufs.copy(out->normal, d.normal, 3 * n));
+    if (out->albedo) HIP_TRY(bufs.copy(out->albedo, d.albedo, 3 * n));
+    return SRT_OK;
+}
+
+int srt_denoise(srt_ctx* c, int32_t width, int32_t height, const srt_denoise_args* a) {
+    if (!c || !a) return fail(SRT_ERR_ARG, "null argument");
+    if (width <= 0 || height <= 0) return fail(SRT_ERR_ARG, "srt_denoise: non-positive image size");
+    if (!a->rgb || !a->normal || !a->albedo || !a->position || !a->depth)
+        return fail(SRT_ERR_ARG, "srt_denoise: NULL colour or guide array");
+    if (a->levels < 0 || a->levels > SRT_DENOISE_MAX_LEVELS) return fail(SRT_ERR_ARG, "srt_denoise: levels outside 0..8");
+    if (!(a->sigma_color > 0.0) || !(a->sigma_normal > 0.0) || !(a->sigma_albedo > 0.0) || !(a->sigma_plane > 0.0))
+        return fail(SRT_ERR_ARG, "srt_denoise: sigmas must be positive");
+    if (a->flags & ~SRT_DENOISE_RGBX) return fail(SRT_ERR_ARG, "srt_denoise: unknown flag");
+    if (!a->out_rgb && !a->out_srgb8) return fail(SRT_ERR_ARG, "srt_denoise: no output");
+    HIP_TRY(hipSetDevice(c->device));
+    DevList bufs;
+    const int64_t n = (int64_t)width * height;
+    AtrousPlanes G{};
+    G.npix = n;
+    G.W = width;
+    HIP_TRY(stage_in(bufs, a->rgb, 3 * n, &G.rgb));
+    HIP_TRY(stage_in(bufs, a->normal, 3 * n, &G.normal));
+    HIP_TRY(stage_in(bufs, a->albedo, 3 * n, &G.albedo));
+    HIP_TRY(stage_in(bufs, a->position, 3 * n, &G.position));
+    HIP_TRY(stage_in(bufs, a->depth, n, &G.depth));
+    double* pong[2] = {nullptr, nullptr};  // the levels' colour buffers
+    for (int k = 0; k < std::min(a->levels, 2); ++k) HIP_TRY(bufs.alloc(&pong[k], 3 * n));
+    const bool rgbx = (a->flags & SRT_DENOISE_RGBX) != 0;
+    const int64_t u8_bytes = n * (rgbx ? 4 : 3);
+    uint8_t* du8 = nullptr;
+    if (a->out_srgb8) {
+        if (is_device_ptr(a->out_srgb8))
+            du8 = a->out_srgb8;
+        else
+            HIP_TRY(bufs.alloc(&du8, u8_bytes));
+    }
+    EventList ev;
+    if (a->ms_levels) HIP_TRY(ev.create(a->levels + 2));
+    hipStream_t st = c->f->stream;
+    const int64_t segs = ((int64_t)width + 63) / 64;
+    const int grid = grid_for(segs * height * 64, c->max_blocks);
+    if (a->ms_levels) HIP_TRY(hipEventRecord(ev.e[0], st));
+    for (int l = 0; l < a->levels; ++l) {
+        AtrousLevel K{};
+        K.W = width, K.H = height, K.step = 1 << l;
+        const double sc = a->sigma_color * ldexp(1.0, -l);
+        K.sc2 = sc * sc;
+        K.sn2 = a->sigma_normal * a->sigma_normal;
+        K.sa2 = a->sigma_albedo * a->sigma_albedo;
+        K.sp2 = a->sigma_plane * a->sigma_plane;
+        hipLaunchKernelGGL(k_atrous, dim3(grid), dim3(DN_BLOCK), 0, st, G, K, pong[l & 1]);
+        HIP_TRY(hipGetLastError());
+        if (a->ms_levels) HIP_TRY(hipEventRecord(ev.e[(size_t)l + 1], st));
+        G.rgb = pong[l & 1];
+    }
+    if (du8) {
+        hipLaunchKernelGGL(k_denoise_resolve, dim3(grid_for(n, c->max_blocks)), dim3(DN_BLOCK), 0, st, G.rgb, n, du8,
+                           rgbx ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+    }
+    if (a->ms_levels) HIP_TRY(hipEventRecord(ev.e[(size_t)a->levels + 1], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int l = 0; l <= a->levels && a->ms_levels; ++l) {
+        // each level, then the whole chain (first launch to the end of the resolve)
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ev.e[l < a->levels ? (size_t)l : 0], ev.e[(size_t)l + 1]));
+        a->ms_levels[l] = ms;
+    }
+    if (a->out_rgb && a->out_rgb != G.rgb) HIP_TRY(bufs.copy(a->out_rgb, G.rgb, 3 * n));
+    if (a->out_srgb8 && du8 != a->out_srgb8) HIP_TRY(bufs.copy(a->out_srgb8, (const uint8_t*)du8, u8_bytes));
     return SRT_OK;
 }
 

@@ -505,6 +505,95 @@ def texture_lookup(u8, repeat, u, v, linear=True):
     return out
 
 
+def denoise_params(spec):
+    """Scene.render's `denoise` argument -> the filter's parameters (N.DENOISE_DEFAULTS overridden by a
+    dict), or None for no denoising.  ValueError for an unknown key or a value srt_denoise would refuse."""
+    if spec is None or spec is False:
+        return None
+    params = dict(N.DENOISE_DEFAULTS)
+    if spec is True:
+        return params
+    if not isinstance(spec, dict):
+        raise ValueError("denoise must be a bool or a dict of %s" % sorted(params))
+    for k, v in spec.items():
+        if k not in params:
+            raise ValueError("denoise: unknown key %r (known: %s)" % (k, ", ".join(sorted(params))))
+        if k == "levels":
+            if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= N.DENOISE_MAX_LEVELS:
+                raise ValueError("denoise: levels must be an integer in 0..%d, not %r" % (N.DENOISE_MAX_LEVELS, v))
+            params[k] = int(v)
+        else:
+            if isinstance(v, bool) or not float(v) > 0.0 or float(v) == float("inf"):
+                raise ValueError("denoise: %s must be a positive number, not %r" % (k, v))
+            params[k] = float(v)
+    return params
+
+
+def render_aovs(scene, ctx=None):
+    """The first-hit guide images of `scene` (srt_render_aovs), one pixel-centre pinhole ray per pixel:
+    {"hit_id" (n,) int32, "depth" (n,), "position" / "normal" / "albedo" (3, n), "ms_kernel"}.  Draws
+    nothing from numpy's RNG.  `ctx`: another context than the process's (a multi-GPU group's first)."""
+    lib = library()
+    if ctx is None:
+        ctx = context()[1]
+    upload(scene, ctx=ctx)
+    cd = camera_desc(scene.camera)
+    n = int(scene.camera.screen_width) * int(scene.camera.screen_height)
+    res = {"hit_id": np.empty(n, dtype=np.int32), "depth": np.empty(n), "position": np.empty((3, n)),
+           "normal": np.empty((3, n)), "albedo": np.empty((3, n))}
+    out = N.AovOut()
+    for k, v in res.items():
+        setattr(out, k, N.ptr(v))
+    N.check(lib, lib.srt_render_aovs(ctx, ctypes.byref(cd), ctypes.byref(out)))
+    res["ms_kernel"] = float(out.ms_kernel)
+    return res
+
+
+def denoise(rgb, aovs, width, height, levels=N.DENOISE_DEFAULTS["levels"],
+            sigma_color=N.DENOISE_DEFAULTS["sigma_color"], sigma_normal=N.DENOISE_DEFAULTS["sigma_normal"],
+            sigma_albedo=N.DENOISE_DEFAULTS["sigma_albedo"], sigma_plane=N.DENOISE_DEFAULTS["sigma_plane"],
+            want_u8=True, rgbx=False, out_u8=None, timings=None, ctx=None):
+    """The a-trous filter of srt_denoise over the linear RGB `rgb` (3, n) with the guides `aovs`
+    ("normal", "albedo", "position" (3, n), "depth" (n,); render_aovs' dict or the caller's own arrays).
+    Returns (filtered rgb (3, n), uint8 image (height, width, 3 or 4) or None).  `out_u8`: a host uint8
+    array to write the image into; `timings`: a list that receives each level's kernel time and then the whole
+    chain's (first launch to the end of the resolve), ms by HIP events;
+    `ctx`: another context than the process's."""
+    lib = library()
+    if ctx is None:
+        ctx = context()[1]
+    W, H = int(width), int(height)
+    n = W * H
+    planes = {}
+    for k, rows in (("rgb", 3), ("normal", 3), ("albedo", 3), ("position", 3), ("depth", 1)):
+        v = np.ascontiguousarray(rgb if k == "rgb" else aovs[k], dtype=np.float64)
+        if v.size != rows * n:
+            raise ValueError("denoise: %s must hold %d x %d values" % (k, rows, n))
+        planes[k] = v
+    a = N.DenoiseArgs()
+    for k, v in planes.items():
+        setattr(a, k, N.ptr(v))
+    a.levels = int(levels)
+    a.flags = N.DENOISE_RGBX if rgbx else 0
+    a.sigma_color, a.sigma_normal = float(sigma_color), float(sigma_normal)
+    a.sigma_albedo, a.sigma_plane = float(sigma_albedo), float(sigma_plane)
+    out = np.empty((3, n))
+    ch = 4 if rgbx else 3
+    u8 = None
+    if out_u8 is not None:
+        if out_u8.dtype != np.uint8 or out_u8.size != ch * n or not out_u8.flags.c_contiguous:
+            raise ValueError("out_u8 must be a contiguous uint8 array of %d bytes" % (ch * n))
+        u8 = out_u8.reshape(n, ch)
+    elif want_u8:
+        u8 = np.empty((n, ch), dtype=np.uint8)
+    ms = np.zeros(max(a.levels, 0) + 1) if timings is not None else None
+    a.out_rgb, a.out_srgb8, a.ms_levels = N.ptr(out), N.ptr(u8), N.ptr(ms)
+    N.check(lib, lib.srt_denoise(ctx, W, H, ctypes.byref(a)))
+    if timings is not None:
+        timings.extend(float(v) for v in ms)
+    return out, (None if u8 is None else u8.reshape(H, W, ch))
+
+
 def primary_rays(camera, jitter):
     """Camera.get_ray geometry for one sample; jitter (4, H*W).  Returns (origin, dir) vec3."""
     lib, ctx = context()

@@ -63,7 +63,7 @@ class Scene:
         self.scene_primitives += [primitive]
         self.collider_list += primitive.collider_list
 
-    def render(self, samples_per_pixel, progress_bar=False, batch_size=None, rng="numpy", seed=None):
+    def render(self, samples_per_pixel, progress_bar=False, batch_size=None, rng="numpy", seed=None, denoise=False):
         """Render `samples_per_pixel` samples and return a PIL RGB image.
 
         rng="numpy" (default) draws the primary-ray jitter from numpy's global legacy RNG exactly
@@ -85,10 +85,22 @@ class Scene:
         host-driven recursion of `_hybrid.py` (their methods on the host, every built-in step on the
         device; a user texture's colour and a user light's distance and irradiance reach the device
         shaders per hit).
+
+        `denoise` (no reference counterpart): True filters the frame on the GPU before it is resolved
+        -- the first-hit normal, albedo, position and depth images of the scene (`get_aovs`) guide an
+        edge-avoiding a-trous wavelet filter over the linear RGB (srt_denoise) -- which makes a frame
+        of few samples usable; a dict overrides the filter's `levels` (0..8) and `sigma_color`,
+        `sigma_normal`, `sigma_albedo`, `sigma_plane` (an unknown key or a bad value raises ValueError
+        before anything runs).  The samples are drawn and traced exactly as without it, and numpy's
+        RNG is left in the same state.  Not available for a scene with user subclasses
+        (NotImplementedError).
         """
         from . import _backend as B
         from . import _hybrid
 
+        dn = B.denoise_params(denoise)
+        if dn is not None:
+            return self._render_denoised(samples_per_pixel, batch_size, rng, seed, dn)
         print("Rendering...")
         t0 = time.time()
         if rng not in ("numpy", "numpy-host", "device"):
@@ -126,6 +138,61 @@ class Scene:
         self.last_stats = out.stats
         print("Render Took", time.time() - t0)
         return Image.fromarray(out.srgb8, "RGB")
+
+    def _render_denoised(self, samples_per_pixel, batch_size, rng, seed, params):
+        """render(denoise=...): the frame as render() traces it with the linear RGB kept, the guide
+        images, the filter; the image is the filter's own resolve (srt_denoise out_srgb8)."""
+        from . import _backend as B
+        from . import _hybrid
+
+        if rng not in ("numpy", "numpy-host", "device"):
+            raise ValueError("rng must be 'numpy', 'numpy-host' or 'device'")
+        if _hybrid.is_hybrid(self):
+            raise NotImplementedError("denoise: a scene with user Collider / Material / texture / Light subclasses "
+                                      "is shaded through the host; its guide images are not computed on the device")
+        print("Rendering...")
+        t0 = time.time()
+        H, W = int(self.camera.screen_height), int(self.camera.screen_width)
+        ndev = len(B.devices())
+        ctx = None
+        if ndev > 1 and rng != "numpy-host" and H >= 8 * ndev:
+            # the gathered frame is filtered on the group's first GPU
+            out = B.render_group(self, samples_per_pixel, seed=seed, batch_size=batch_size, want_rgb=True,
+                                 mt=(rng == "numpy"))
+            import ctypes
+
+            ctx = ctypes.c_void_p(B.group()[1][0])
+        else:
+            jitter = None
+            if rng == "numpy-host":
+                jitter = self.camera.draw_jitter(samples_per_pixel)
+                self.camera.draw_jitter(1)  # reference draws one more get_ray for sizing (scene.py:81)
+            out = B.render_scene(self, samples_per_pixel, jitter=jitter, seed=seed, batch_size=batch_size,
+                                 want_rgb=True, mt=(rng == "numpy"))
+        aovs = B.render_aovs(self, ctx=ctx)
+        blk = B.image_block(4 * W * H)
+        ms = []
+        _, u8 = B.denoise(out.rgb, aovs, W, H, rgbx=True, out_u8=blk, timings=ms, ctx=ctx, **params)
+        self.last_stats = dict(out.stats, denoise=dict(params, ms_aov_kernel=aovs["ms_kernel"], ms_levels=ms[:-1],
+                                                            ms_filter=ms[-1]))
+        print("Render Took", time.time() - t0)
+        return B.rgb_image(u8, W, H, mapped=blk is not None)
+
+    def get_aovs(self):
+        """The first-hit guide images a denoiser needs (no reference counterpart), computed on the GPU
+        from one pixel-centre pinhole ray per pixel -- no random numbers are drawn: a dict of
+        "hit_id" (n,) int32 (index into collider_list, -1 = nothing hit), "depth" (n,) (1e39 = nothing
+        hit), "position", "normal" and "albedo" (3, n), n = screen_width * screen_height, row-major.
+        Pixels that see the background have normal, albedo and position (0, 0, 0)."""
+        from . import _backend as B
+        from . import _hybrid
+
+        if _hybrid.is_hybrid(self):
+            raise NotImplementedError("get_aovs: a scene with user Collider / Material / texture / Light subclasses "
+                                      "is shaded through the host; its guide images are not computed on the device")
+        aovs = B.render_aovs(self)
+        aovs.pop("ms_kernel")
+        return aovs
 
     def get_distances(self):
         """Grey depth map of one primary sample (reference scene.py:142-166)."""
