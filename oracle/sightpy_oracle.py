@@ -22,7 +22,7 @@ Random numbers.  By default every draw comes from numpy's global RNG in the refe
 (camera jitter, `mixed_pdf`/`cosine_pdf`/`spherical_caps_pdf` draws, the `mc=True` pick), which is
 what pins this module to the reference.  With `rng=DeviceStream(seed)` the Monte-Carlo draws
 instead come from the device's counter-based stream -- Philox4x32-10 keyed by (seed, global pixel,
-child-path hash, tag), restated here from csrc/rt_device.h and rt_kernels.hip -- so the GPU's
+child-path hash, tag), restated here from csrc/rt_device.h and rt_trace_common.h -- so the GPU's
 Monte-Carlo paths can be compared with this restatement sample for sample (tests/test_gpu_mc.py).
 The algorithm code is the same in both modes; only the source of the uniforms differs.
 """
@@ -118,7 +118,7 @@ class DeviceStream:
 
 
     def jitter(self, npix, spp, sample_base=0):
-        """The camera uniforms of the device-RNG render mode (render jitter NULL; rt_kernels.hip
+        """The camera uniforms of the device-RNG render mode (render jitter NULL; rt_trace_common.h
         primary_uniforms): pixel p, sample s -> pairs 0, 1 of Rng(seed, p, sample_base + s, TAG_RAYGEN)."""
         pix = np.arange(npix, dtype=np.uint32)
         out = np.empty((spp, 4, npix))

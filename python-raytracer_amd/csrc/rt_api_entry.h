@@ -1,0 +1,337 @@
+// rt_api_entry.h -- entry points of one kernel each: srt_nearest, srt_intersect_collider,
+// srt_collider_surface, srt_texture_lookup, srt_material_normal, srt_primary_rays; the first-hit AOVs and
+// the denoiser (srt_render_aovs, srt_denoise; kernels in rt_denoise.h); device memory for the caller
+// (srt_device_alloc, srt_device_free, srt_memcpy); srt_mt19937_uniforms.
+// A fragment of rt_kernels.hip, included at its end and not compiled alone.  Before it: what stands above
+// its include in rt_kernels.hip; it uses (the API kernels, run_kernel, EventList, stage_in, finish_async, mt_launch).
+extern "C" {
+
+int srt_nearest(srt_ctx* c, const double* O, const double* D, int64_t n, double* t, int32_t* id, double* orient) {
+    if (!c || !O || !D) return fail(SRT_ERR_ARG, "null argument");
+    if (!c->has_scene) return fail(SRT_ERR_NOSCENE, "no scene uploaded");
+    if (n <= 0) return SRT_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    DevList bufs;
+    double *dO, *dD, *dt, *dor;
+    int32_t* did;
+    HIP_TRY(bufs.in(&dO, O, 3 * n));
+    HIP_TRY(bufs.in(&dD, D, 3 * n));
+    HIP_TRY(bufs.alloc(&dt, n));
+    HIP_TRY(bufs.alloc(&dor, n));
+    HIP_TRY(bufs.alloc(&did, n));
+    if (int rc = run_kernel(c, n, nullptr, nullptr, k_nearest, c->S, dO, dD, n, dt, did, dor)) return rc;
+    if (t) HIP_TRY(bufs.copy(t, dt, n));
+    if (id) HIP_TRY(bufs.copy(id, did, n));
+    if (orient) HIP_TRY(bufs.copy(orient, dor, n));
+    return SRT_OK;
+}
+
+int srt_intersect_collider(srt_ctx* c, const srt_collider* col, const double* O, const double* D, int64_t n,
+                           double* out) {
+    if (!c || !col || !O || !D || !out) return fail(SRT_ERR_ARG, "null argument");
+    if (col->type < 0 || col->type > 3) return fail(SRT_ERR_ARG, "bad collider type");
+    if (n <= 0) return SRT_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    DevList bufs;
+    double *dO, *dD, *dout;
+    srt_collider* dcol;
+    HIP_TRY(bufs.in(&dO, O, 3 * n));
+    HIP_TRY(bufs.in(&dD, D, 3 * n));
+    HIP_TRY(bufs.alloc(&dout, 2 * n));
+    HIP_TRY(bufs.in(&dcol, col, 1));
+    if (int rc = run_kernel(c, n, nullptr, nullptr, k_intersect_one, dcol, dO, dD, n, dout)) return rc;
+    HIP_TRY(bufs.copy(out, dout, 2 * n));
+    return SRT_OK;
+}
+
+int srt_collider_surface(srt_ctx* c, const srt_collider* col, const double* P, int64_t n, double* N, double* uv,
+                         int primitive_uv) {
+    if (!c || !col || !P || (!N && !uv)) return fail(SRT_ERR_ARG, "null argument");
+    if (col->type < 0 || col->type > 3) return fail(SRT_ERR_ARG, "bad collider type");
+    if (uv && col->type == SRT_TRIANGLE && !(col->flags & SRT_CF_VUV))
+        return fail(SRT_ERR_ARG, "Triangle uv is undefined in the reference (triangle.py:79-83)");
+    if (n <= 0) return SRT_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    DevList bufs;
+    srt_collider rec = *col;
+    if (!primitive_uv) rec.flags &= ~SRT_CF_UV_CROSS;  // the collider's own 4x3 cross coordinates
+    double *dP, *dN = nullptr, *duv = nullptr;
+    srt_collider* dcol;
+    HIP_TRY(bufs.in(&dP, P, 3 * n));
+    if (N) HIP_TRY(bufs.alloc(&dN, 3 * n));
+    if (uv) HIP_TRY(bufs.alloc(&duv, 2 * n));
+    HIP_TRY(bufs.in(&dcol, &rec, 1));
+    if (int rc = run_kernel(c, n, nullptr, nullptr, k_collider_surface, dcol, dP, n, dN, duv)) return rc;
+    if (N) HIP_TRY(bufs.copy(N, dN, 3 * n));
+    if (uv) HIP_TRY(bufs.copy(uv, duv, 2 * n));
+    return SRT_OK;
+}
+
+int srt_texture_lookup(srt_ctx* c, const srt_texture* tex, const uint8_t* texels, int64_t texel_bytes,
+                       const double* uv, int64_t n, double* rgb) {
+    if (!c || !tex || !texels || !uv || !rgb) return fail(SRT_ERR_ARG, "null argument");
+    if (tex->offset < 0 || tex->offset + tex->height * tex->width * tex->channels > texel_bytes)
+        return fail(SRT_ERR_ARG, "texture record outside the texel array");
+    if (n <= 0) return SRT_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    DevList bufs;
+    uint8_t* dtexels;
+    srt_texture* dtex;
+    double *duv, *drgb;
+    uint32_t* dflags;
+    HIP_TRY(bufs.in(&dtexels, texels, texel_bytes));
+    HIP_TRY(bufs.in(&dtex, tex, 1));
+    HIP_TRY(bufs.in(&duv, uv, 2 * n));
+    HIP_TRY(bufs.alloc(&drgb, 3 * n));
+    HIP_TRY(bufs.alloc(&dflags, 1));
+    HIP_TRY(hipMemset(dflags, 0, 4));
+    SceneView S{};
+    S.tex = (const RT_RO srt_texture*)dtex;
+    S.texels = (const RT_RO uint8_t*)dtexels;
+    S.ntex = 1;
+    int flag_rc = SRT_OK;
+    if (int rc = run_kernel(c, n, dflags, &flag_rc, k_texture_lookup, S, duv, n, drgb, dflags)) return rc;
+    HIP_TRY(bufs.copy(rgb, drgb, 3 * n));
+    return flag_rc;
+}
+
+int srt_material_normal(srt_ctx* c, const srt_collider* col, const srt_texture* normalmap, const uint8_t* texels,
+                        int64_t texel_bytes, const double* P, const double* orient, int64_t n, double* N) {
+    if (!c || !col || !P || !orient || !N) return fail(SRT_ERR_ARG, "null argument");
+    if (col->type < 0 || col->type > 3) return fail(SRT_ERR_ARG, "bad collider type");
+    if (normalmap) {
+        if (!texels || normalmap->offset < 0 || normalmap->channels < 3 || normalmap->channel0 < 0 ||
+            normalmap->channel0 + 3 > normalmap->channels ||
+            normalmap->offset + (int64_t)normalmap->height * normalmap->width * normalmap->channels > texel_bytes)
+            return fail(SRT_ERR_ARG, "normal-map record outside the texel array");
+        if (col->type != SRT_PLANE && col->type != SRT_CUBOID)
+            return fail(SRT_ERR_ARG, "a normal map needs the collider's inverse_basis_matrix (Plane, Cuboid)");
+    }
+    if (n <= 0) return SRT_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    DevList bufs;
+    srt_material mrec{};
+    mrec.type = SRT_GLOSSY;
+    mrec.tex = mrec.tex_aux0 = mrec.tex_aux1 = -1;
+    mrec.normalmap = normalmap ? 0 : -1;
+    srt_collider* dcol;
+    srt_material* dmat;
+    srt_texture* dtex = nullptr;
+    uint8_t* dtexels = nullptr;
+    double *dP, *dor, *dN;
+    uint32_t* dflags;
+    HIP_TRY(bufs.in(&dcol, col, 1));
+    HIP_TRY(bufs.in(&dmat, &mrec, 1));
+    HIP_TRY(bufs.in(&dP, P, 3 * n));
+    HIP_TRY(bufs.in(&dor, orient, n));
+    HIP_TRY(bufs.alloc(&dN, 3 * n));
+    HIP_TRY(bufs.alloc(&dflags, 1));
+    HIP_TRY(hipMemset(dflags, 0, 4));
+    SceneView S{};
+    if (normalmap) {
+        HIP_TRY(bufs.in(&dtex, normalmap, 1));
+        HIP_TRY(bufs.in(&dtexels, texels, texel_bytes));
+        S.tex = (const RT_RO srt_texture*)dtex;
+        S.texels = (const RT_RO uint8_t*)dtexels;
+        S.ntex = 1;
+    }
+    int flag_rc = SRT_OK;
+    if (int rc = run_kernel(c, n, dflags, &flag_rc, k_material_normal, S, dcol, dmat, dP, dor, n, dN, dflags)) return rc;
+    HIP_TRY(bufs.copy(N, dN, 3 * n));
+    return flag_rc;
+}
+
+int srt_primary_rays(srt_ctx* c, const srt_camera* cam, const double* J, double* O, double* D) {
+    if (!c || !cam || !J || !O || !D) return fail(SRT_ERR_ARG, "null argument");
+    HIP_TRY(hipSetDevice(c->device));
+    DevList bufs;
+    const int64_t n = (int64_t)cam->width * cam->height;
+    double *dJ, *dO, *dD, *xs, *ys;
+    HIP_TRY(bufs.in(&dJ, J, 4 * n));
+    HIP_TRY(bufs.alloc(&dO, 3 * n));
+    HIP_TRY(bufs.alloc(&dD, 3 * n));
+    HIP_TRY(bufs.in(&xs, cam->xs, cam->width));
+    HIP_TRY(bufs.in(&ys, cam->ys, cam->height));
+    srt_camera k = *cam;
+    k.xs = xs;
+    k.ys = ys;
+    if (int rc = run_kernel(c, n, nullptr, nullptr, k_primary_rays, k, dJ, n, dO, dD)) return rc;
+    HIP_TRY(bufs.copy(O, dO, 3 * n));
+    HIP_TRY(bufs.copy(D, dD, 3 * n));
+    return SRT_OK;
+}
+
+// ---- denoising (rt_denoise.h) -----------------------------------------------------------------------
+int srt_render_aovs(srt_ctx* c, const srt_camera* cam, srt_aov_out* out) {
+    if (!c || !cam || !out) return fail(SRT_ERR_ARG, "null argument");
+    if (!c->has_scene) return fail(SRT_ERR_NOSCENE, "no scene uploaded");
+    if (cam->width <= 0 || cam->height <= 0 || !cam->xs || !cam->ys) return fail(SRT_ERR_ARG, "bad camera");
+    if (std::find(c->col_hit_albedo.begin(), c->col_hit_albedo.end(), 1) != c->col_hit_albedo.end())
+        return fail(SRT_ERR_ARG, "srt_render_aovs: the scene holds an SRT_MF_HIT_ALBEDO material (a user texture: "
+                                 "its albedo is not known to the device)");
+    HIP_TRY(hipSetDevice(c->device));
+    DevList bufs;
+    const int64_t n = (int64_t)cam->width * cam->height;
+    AovOut d{};
+    if (out->hit_id) HIP_TRY(bufs.alloc(&d.hit_id, n));
+    if (out->depth) HIP_TRY(bufs.alloc(&d.depth, n));
+    if (out->position) HIP_TRY(bufs.alloc(&d.position, 3 * n));
+    if (out->normal) HIP_TRY(bufs.alloc(&d.normal, 3 * n));
+    if (out->albedo) HIP_TRY(bufs.alloc(&d.albedo, 3 * n));
+    double *xs, *ys;
+    uint32_t* dflags;
+    HIP_TRY(bufs.in(&xs, cam->xs, cam->width));
+    HIP_TRY(bufs.in(&ys, cam->ys, cam->height));
+    HIP_TRY(bufs.alloc(&dflags, 1));
+    HIP_TRY(hipMemset(dflags, 0, 4));
+    srt_camera k = *cam;
+    k.xs = xs;
+    k.ys = ys;
+    SceneView S = c->S;
+    S.nlut_lds = 0;  // (k_aov stages no texture tables in LDS: it reads them from the texture records)
+    EventList ev;
+    HIP_TRY(ev.create(2));
+    hipStream_t st = c->f->stream;
+    HIP_TRY(hipEventRecord(ev.e[0], st));
+    hipLaunchKernelGGL(k_aov, dim3(grid_for(n, c->max_blocks)), dim3(DN_BLOCK), 0, st, S, k, d, dflags);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev.e[1], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+    out->ms_kernel = ms;
+    uint32_t flags = 0;
+    HIP_TRY(hipMemcpy(&flags, dflags, 4, hipMemcpyDefault));
+    if (int rc = check_flags(flags)) return rc;
+    if (out->hit_id) HIP_TRY(bufs.copy(out->hit_id, d.hit_id, n));
+    if (out->depth) HIP_TRY(bufs.copy(out->depth, d.depth, n));
+    if (out->position) HIP_TRY(bufs.copy(out->position, d.position, 3 * n));
+    if (out->normal) HIP_TRY(bufs.copy(out->normal, d.normal, 3 * n));
+    if (out->albedo) HIP_TRY(bufs.copy(out->albedo, d.albedo, 3 * n));
+    return SRT_OK;
+}
+
+int srt_denoise(srt_ctx* c, int32_t width, int32_t height, const srt_denoise_args* a) {
+    if (!c || !a) return fail(SRT_ERR_ARG, "null argument");
+    if (width <= 0 || height <= 0) return fail(SRT_ERR_ARG, "srt_denoise: non-positive image size");
+    if (!a->rgb || !a->normal || !a->albedo || !a->position || !a->depth)
+        return fail(SRT_ERR_ARG, "srt_denoise: NULL colour or guide array");
+    if (a->levels < 0 || a->levels > SRT_DENOISE_MAX_LEVELS) return fail(SRT_ERR_ARG, "srt_denoise: levels outside 0..8");
+    if (!(a->sigma_color > 0.0) || !(a->sigma_normal > 0.0) || !(a->sigma_albedo > 0.0) || !(a->sigma_plane > 0.0))
+        return fail(SRT_ERR_ARG, "srt_denoise: sigmas must be positive");
+    if (a->flags & ~SRT_DENOISE_RGBX) return fail(SRT_ERR_ARG, "srt_denoise: unknown flag");
+    if (!a->out_rgb && !a->out_srgb8) return fail(SRT_ERR_ARG, "srt_denoise: no output");
+    HIP_TRY(hipSetDevice(c->device));
+    DevList bufs;
+    const int64_t n = (int64_t)width * height;
+    AtrousPlanes G{};
+    G.npix = n;
+    G.W = width;
+    HIP_TRY(stage_in(bufs, a->rgb, 3 * n, &G.rgb));
+    HIP_TRY(stage_in(bufs, a->normal, 3 * n, &G.normal));
+    HIP_TRY(stage_in(bufs, a->albedo, 3 * n, &G.albedo));
+    HIP_TRY(stage_in(bufs, a->position, 3 * n, &G.position));
+    HIP_TRY(stage_in(bufs, a->depth, n, &G.depth));
+    double* pong[2] = {nullptr, nullptr};  // the levels' colour buffers
+    for (int k = 0; k < std::min(a->levels, 2); ++k) HIP_TRY(bufs.alloc(&pong[k], 3 * n));
+    const bool rgbx = (a->flags & SRT_DENOISE_RGBX) != 0;
+    const int64_t u8_bytes = n * (rgbx ? 4 : 3);
+    uint8_t* du8 = nullptr;
+    if (a->out_srgb8) {
+        if (is_device_ptr(a->out_srgb8))
+            du8 = a->out_srgb8;
+        else
+            HIP_TRY(bufs.alloc(&du8, u8_bytes));
+    }
+    EventList ev;
+    if (a->ms_levels) HIP_TRY(ev.create(a->levels + 2));
+    hipStream_t st = c->f->stream;
+    const int64_t segs = ((int64_t)width + 63) / 64;
+    const int grid = grid_for(segs * height * 64, c->max_blocks);
+    if (a->ms_levels) HIP_TRY(hipEventRecord(ev.e[0], st));
+    for (int l = 0; l < a->levels; ++l) {
+        AtrousLevel K{};
+        K.W = width, K.H = height, K.step = 1 << l;
+        const double sc = a->sigma_color * ldexp(1.0, -l);
+        K.sc2 = sc * sc;
+        K.sn2 = a->sigma_normal * a->sigma_normal;
+        K.sa2 = a->sigma_albedo * a->sigma_albedo;
+        K.sp2 = a->sigma_plane * a->sigma_plane;
+        hipLaunchKernelGGL(k_atrous, dim3(grid), dim3(DN_BLOCK), 0, st, G, K, pong[l & 1]);
+        HIP_TRY(hipGetLastError());
+        if (a->ms_levels) HIP_TRY(hipEventRecord(ev.e[(size_t)l + 1], st));
+        G.rgb = pong[l & 1];
+    }
+    if (du8) {
+        hipLaunchKernelGGL(k_denoise_resolve, dim3(grid_for(n, c->max_blocks)), dim3(DN_BLOCK), 0, st, G.rgb, n, du8,
+                           rgbx ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+    }
+    if (a->ms_levels) HIP_TRY(hipEventRecord(ev.e[(size_t)a->levels + 1], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int l = 0; l <= a->levels && a->ms_levels; ++l) {
+        // each level, then the whole chain (first launch to the end of the resolve)
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ev.e[l < a->levels ? (size_t)l : 0], ev.e[(size_t)l + 1]));
+        a->ms_levels[l] = ms;
+    }
+    if (a->out_rgb && a->out_rgb != G.rgb) HIP_TRY(bufs.copy(a->out_rgb, G.rgb, 3 * n));
+    if (a->out_srgb8 && du8 != a->out_srgb8) HIP_TRY(bufs.copy(a->out_srgb8, (const uint8_t*)du8, u8_bytes));
+    return SRT_OK;
+}
+
+int srt_device_alloc(srt_ctx* c, int64_t bytes, void** out) {
+    if (!c || !out || bytes <= 0) return fail(SRT_ERR_ARG, "bad argument");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMalloc(out, (size_t)bytes));
+    return SRT_OK;
+}
+
+int srt_device_free(srt_ctx* c, void* p) {
+    if (!c) return fail(SRT_ERR_ARG, "null ctx");
+    HIP_TRY(hipSetDevice(c->device));
+    if (p) HIP_TRY(hipFree(p));
+    return SRT_OK;
+}
+
+int srt_memcpy(srt_ctx* c, void* dst, const void* src, int64_t bytes) {
+    if (!c || !dst || !src || bytes < 0) return fail(SRT_ERR_ARG, "bad argument");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpy(dst, src, (size_t)bytes, hipMemcpyDefault));
+    return SRT_OK;
+}
+
+int srt_mt19937_uniforms(srt_ctx* c, const uint32_t* key, int32_t pos, int64_t n_out, int64_t n_skip, double* out,
+                         uint32_t* key_out, int32_t* pos_out) {
+    if (!c || !key || !key_out || !pos_out || (n_out > 0 && !out)) return fail(SRT_ERR_ARG, "null argument");
+    c->pf.valid = false;  // (generates from the stream state a prefetch assumed)
+    if (pos < 0 || pos > rtmt::N || n_out < 0 || n_skip < 0) return fail(SRT_ERR_ARG, "bad position or count");
+    if (is_device_ptr(key) || is_device_ptr(key_out)) return fail(SRT_ERR_ARG, "key and key_out are host arrays");
+    if (n_out + n_skip == 0) {
+        memcpy(key_out, key, rtmt::N * 4);
+        *pos_out = pos;
+        return SRT_OK;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = finish_async(c, nullptr);  // frames in flight may use the generator's scratch
+    if (rc) return rc;
+    if ((rc = mt_ensure(c))) return rc;
+    double* dst = out;
+    const bool host_out = n_out > 0 && !is_device_ptr(out);
+    if (host_out) {
+        if ((rc = c->mt_out.ensure(n_out))) return rc;
+        dst = c->mt_out;
+    }
+    hipStream_t st = c->f->stream;
+    HIP_TRY(hipMemcpyAsync(mt_key0(c), key, rtmt::N * 4, hipMemcpyHostToDevice, st));
+    int final_pos = 0;
+    if ((rc = mt_win_ensure(c, *c->f, (int64_t)rtmt::SEGS * rtmt::N))) return rc;
+    if ((rc = mt_launch(c, st, c->f->mt_win, mt_key0(c), pos, n_out, n_skip, dst, &final_pos))) return rc;
+    if (host_out) HIP_TRY(hipMemcpyAsync(out, dst, (size_t)n_out * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(key_out, mt_dump(c), rtmt::N * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *pos_out = final_pos;
+    return SRT_OK;
+}
+
+}  // extern "C"

@@ -1088,7 +1088,7 @@ RT_HD int nearest_hit(const SceneView& S, d3 O, d3 D, double& tn, double& on, bo
 //   em.child(ch)       one child ray (weight relative to the parent's throughput)
 //   em.diffuse(g, m)   a Diffuse fan-out of g.count children (generated by diffuse_child)
 //   em.shadow(n)       n shadow rays were traced
-// On the GPU the emitter appends children with one atomic per wave (rt_kernels.hip); in the host
+// On the GPU the emitter appends children with one atomic per wave (rt_trace_common.h GpuEmit); in the host
 // check harness it pushes to a vector.  Nothing is held per lane between hits.
 struct Child {
     d3 o, d, w;       // w: weight relative to the parent's throughput

@@ -33,7 +33,7 @@ thread_local bool g_vattr = false;  // the scene of the current call has SRT_CF_
 thread_local bool g_plight = false;  // ... has an SRT_LIGHT_POSITIONAL light
 thread_local std::vector<srt_light> g_lights;  // its light table as the kernels read it (pack_lights)
 // rows of the current hc_render (null: identity / hc_trace): Monte-Carlo draws are keyed by the
-// global pixel, as key_pix in rt_kernels.hip
+// global pixel, as key_pix in rt_trace_common.h
 thread_local const int32_t* g_rows = nullptr;
 thread_local int64_t g_width = 0;
 

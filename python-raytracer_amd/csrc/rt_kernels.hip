@@ -1,5 +1,12 @@
 // rt_kernels.hip -- gfx950 ray tracer behind the C ABI of include/sightpy_rt.h: the one translation
-// unit of libsightpy_hip.so (rt_render.h, the host side of srt_render, is included below).
+// unit of libsightpy_hip.so.  Its first and last parts, and the host side of srt_render, are fragments of
+// this unit, included in place (source map, in order):
+//   rt_trace_common.h  fail / HIP_TRY, Queue, TraceParams, key_pix, the fixed-point sums, PixAcc, GpuEmit
+//   (this file)        the kernels, the variants, DevBuf / DevList, the context, the MT host side, scene upload
+//   rt_render.h        render_impl, before srt_render and its siblings; then srt_trace and srt_shade* here
+//   rt_api_entry.h     the single-kernel entry points, AOVs and denoise, device memory, srt_mt19937_uniforms
+//   rt_api_group.h     communicators, srt_render_group*, allreduce, barrier
+//   rt_api_misc.h      host memory, the srt_debug_* hooks, srt_synchronize
 //
 // The reference (sightpy) recursively evaluates numpy batches: intersect every collider, reduce the
 // nearest hit, compact the rays per collider, shade, recurse (ray.py:122-148).  A colour composes
@@ -49,397 +56,9 @@
 using namespace rt;
 using namespace rtmt_dev;
 
+#include "rt_trace_common.h"
+
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                           \
-    do {                                                                                        \
-        hipError_t _e = (expr);                                                                 \
-        if (_e != hipSuccess)                                                                   \
-            return fail(SRT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));        \
-    } while (0)
-
-constexpr int BLOCK = 256;
-#ifndef RT_NSHARD
-#define RT_NSHARD 256
-#endif
-// queue shards, one append counter each: blocks b, b + NSHARD, ... share one.  Appends are
-// device-scope atomics executed at the memory side; with 16 counters their serialisation cost the
-// depth-0 kernel ~40 % (1.39 vs 0.87 ms, ex1 1080p), 64-256 counters remove it.
-constexpr int NSHARD = RT_NSHARD;
-constexpr size_t TRACE_PARAMS_BYTES = 864;
-constexpr int MAX_LUT_LDS = 12;  // texture tables staged in LDS per block (2 KiB each)
-// retry bits of flags[1]: a queue shard / ring overflowed (re-render with bigger queues); a tie gave
-// a chained ray a second child (re-render without chain mode)
-constexpr uint32_t RETRY_OVERFLOW = 1u;
-constexpr uint32_t RETRY_CHAIN_TIE = 2u;
-constexpr uint32_t RETRY_FIXED_RANGE = 4u;  // a contribution beyond the fixed-point range (fx_add)
-
-struct Queue {
-    double *ox, *oy, *oz, *dx, *dy, *dz, *wr, *wg, *wb;
-    uint32_t *pix, *meta, *path;
-};
-constexpr int64_t RAY_BYTES = 9 * 8 + 3 * 4;  // 84 B per queued ray
-
-struct TraceParams {
-    SceneView S;
-    Queue qin, qout;
-    const uint32_t* cnt_in;  // [NSHARD] rays per input shard (depth d)
-    uint32_t* cnt_out;       // [NSHARD] append counters of the output shards (depth d+1)
-    uint32_t* flags;         // [0] error bits, [1] overflow
-    unsigned long long* shadow;
-    double* fb;              // [3][npix] depth-0 colour (stored by the pixel's own thread)
-    unsigned long long* fbx; // [3][npix] fixed-point sums of every added contribution (fb_add), or null:
-                             // f64 atomics into fb (option "deterministic" 0, order-dependent rounding)
-    int64_t npix;
-    int64_t seg;             // capacity of one queue shard (rays)
-    uint64_t seed;
-    int depth;
-    int fb_first;  // depth 0 of the first pass: store the pixel instead of adding (no memset)
-    // primary generation
-    int64_t n_primary;
-    srt_camera cam;
-    const int32_t* rows;
-    const double* jitter;  // [spp][4][jit_plane] (device) or null
-    int64_t jit_plane;     // doubles per jitter plane: npix, or width*height when jit_global
-    int jit_global;        // 1: jitter indexed by the global pixel (the whole frame's numpy stream)
-    int sample_base;
-    int spp;           // samples of this pass (k_primary)
-    int pix_groups;    // k_primary: sample groups per pixel (a power of two <= 64; lanes of one wave)
-    int chain;         // k_trace: trace each ray's whole (single-child) chain in-thread, see k_trace
-    int32_t* hit_out;  // [spp][npix] or null
-    // frame kernel (k_frame): per-wave ray rings in HBM, slot s = rays [s * ring_cap, (s+1) * ring_cap)
-    Queue ring;
-    uint32_t* ring_lock;  // [nslot] 0 = free, 1 = owned by a running wave
-    int64_t ring_cap;     // rays per ring (power of two)
-    double* out_rgb;      // fused resolve (single-pass frames): [3][npix] linear RGB or null
-    uint8_t* out_u8;      //                                     [npix][3] sRGB8 or null
-    int nslot;
-    int dcap;             // deepest depth traced; deeper children are counted and dropped
-    int fuse_resolve;     // 1: k_frame resolves its pixels (no framebuffer); 0: adds to fb
-    int spp_total;        // samples of the frame (resolve average)
-    // k_shade_forced (srt_shade, Material.get_color): the first depth's hit per ray (index = pix)
-    const int32_t* force_id;
-    const double* force_t;
-    const double* force_o;
-    // k_frame sample groups: block b takes tile b % ntiles and the samples [g spg, (g+1) spg) of the
-    // pass, g = b / ntiles; groups > 1 store their partial sums to fbg[g][3][npix] (k_fb_groups adds them)
-    double* fbg;
-    int groups;
-    int ntiles;
-    // srt_debug_lane_stats: [depth][2] u64 = (wave iterations that traced the depth, live lanes in
-    // them) of the fused paths' depth loop, or null (counting off)
-    unsigned long long* lane_stats;
-};
-// k_shade_forced_inputs (srt_shade_level_inputs): what the user's texture / Light methods returned per
-// ray (index = pix, batch of npix), or null.  A kernel argument of its own: the kernels that take
-// TraceParams alone keep their argument block (several copy it to scratch: 24 bytes more there grew
-// their scratch size).
-struct HitPtrs {
-    const double* albedo;  // [3][npix]
-    const double* ldist;   // [user lights][npix]
-    const double* lirr;    // [user lights][3][npix]
-};
-// kernel argument: host and device passes must agree on the layout (catches address-space pointer
-// size differences, see SceneView)
-static_assert(sizeof(TraceParams) == TRACE_PARAMS_BYTES, "TraceParams layout");
-
-// Pixel identity that keys the Monte-Carlo draws: the global pixel row * width + col of the frame
-// (`pix` indexes the rows this call renders), so that an image sharded over any number of GPUs draws
-// the same numbers as the single-GPU render; srt_trace (no rows) keys by the ray's batch index.
-__device__ __forceinline__ uint32_t key_pix(const TraceParams& P, uint32_t pix) {
-    if (!P.rows) return pix;
-    const uint32_t W = (uint32_t)P.cam.width;
-    const uint32_t lr = pix / W;
-    return (uint32_t)P.rows[lr] * W + (pix - lr * W);
-}
-
-__device__ __forceinline__ void queue_store(const Queue& q, int64_t i, d3 o, d3 d, d3 w, uint32_t pix,
-                                            uint32_t meta, uint32_t path) {
-    q.ox[i] = o.x; q.oy[i] = o.y; q.oz[i] = o.z;
-    q.dx[i] = d.x; q.dy[i] = d.y; q.dz[i] = d.z;
-    q.wr[i] = w.x; q.wg[i] = w.y; q.wb[i] = w.z;
-    q.pix[i] = pix; q.meta[i] = meta; q.path[i] = path;
-}
-
-__device__ __forceinline__ Ray queue_load(const Queue& q, int64_t i) {
-    Ray r;
-    r.o = d3{q.ox[i], q.oy[i], q.oz[i]};
-    r.d = d3{q.dx[i], q.dy[i], q.dz[i]};
-    r.w = d3{q.wr[i], q.wg[i], q.wb[i]};
-    r.pix = q.pix[i]; r.meta = q.meta[i]; r.path = q.path[i];
-    return r;
-}
-
-// Contributions added to a pixel by other threads (depth >= 1, split samples) go into an
-// order-independent fixed-point sum, so a frame is bit-reproducible (the reference is
-// deterministic; f64 atomics are not, their rounding depends on arrival order): each contribution
-// rounded to a multiple of 2^-FX_BITS and summed with one int64 atomic per channel (the count of f64
-// atomics it replaces); the resolve adds sum 2^-FX_BITS to the depth-0 colour.  Rounding error
-// <= 2^-45 = 2.8e-14 per contribution; a contribution of magnitude >= 2^17 (sums up to 2^19 stay in
-// range) raises RETRY_FIXED_RANGE and the frame is rendered again with f64 atomics.
-constexpr int FX_BITS = 44;
-constexpr double FX_SCALE = (double)(1ull << FX_BITS);
-constexpr double FX_UNIT = 1.0 / FX_SCALE;
-constexpr double FX_MAX = 131072.0;                 // 2^17
-
-// Range of the sums: a pixel-channel sum wraps only beyond 2^20 (2^64 scaled).  Besides the three
-// sums, every pixel keeps a coarse magnitude -- the f32 sum of |r| + |g| + |b| of its terms, one
-// more fire-and-forget atomic (fx_mag, behind the sums in the same buffer) -- and the resolve
-// distrusts a pixel whose magnitude reached FX_MAG_LIMIT (2^16; f32 rounding keeps it within a factor
-// 1 + n 2^-24 of the true magnitude, so no sum of fewer than 2^23 terms gets near 2^20 unseen).
-// A returning atomic per term (checking each partial sum) cost 6.6 % of the device frame.
-constexpr float FX_MAG_LIMIT = 65536.0f;
-RT_HD int64_t fx_words(int64_t npix) { return 3 * npix + (npix + 1) / 2; }  // u64 words of fbx
-__device__ __forceinline__ float* fx_mag(unsigned long long* fbx, int64_t npix) {
-    return reinterpret_cast<float*>(fbx + 3 * npix);
-}
-__device__ __forceinline__ const float* fx_mag(const unsigned long long* fbx, int64_t npix) {
-    return reinterpret_cast<const float*>(fbx + 3 * npix);
-}
-
-__device__ __forceinline__ bool fx_add(unsigned long long* acc, double v) {
-    if (!(fabs(v) < FX_MAX)) return false;  // (also NaN)
-    atomicAdd(acc, (unsigned long long)__double2ll_rn(v * FX_SCALE));
-    return true;
-}
-
-__device__ __forceinline__ void fb_add(double* fb, unsigned long long* fbx, uint32_t* flags, int64_t npix,
-                                       uint32_t pix, d3 w, d3 c) {
-    if (is_zero(c)) return;  // adding an exact zero is a no-op
-#ifdef RT_ABL_FB  // diagnostic build only: no framebuffer atomics
-    if (w.x * c.x == 12345.678) fb[pix] = 0.0;
-    return;
-#endif
-    if (fbx) {
-        // all three channels added (no short-circuit), then one range check
-        const double tx = w.x * c.x, ty = w.y * c.y, tz = w.z * c.z;
-        const int ok = (int)fx_add(fbx + pix, tx) & (int)fx_add(fbx + npix + pix, ty) & (int)fx_add(fbx + 2 * npix + pix, tz);
-        if (!ok) atomicOr(flags + 1, RETRY_FIXED_RANGE);
-        unsafeAtomicAdd(fx_mag(fbx, npix) + pix, (float)((fabs(tx) + fabs(ty)) + fabs(tz)));
-    } else {
-        unsafeAtomicAdd(fb + pix, w.x * c.x);
-        unsafeAtomicAdd(fb + npix + pix, w.y * c.y);
-        unsafeAtomicAdd(fb + 2 * npix + pix, w.z * c.z);
-    }
-}
-
-__device__ __forceinline__ double fx_value(const unsigned long long* fbx, int64_t npix, int ch, int64_t p) {
-    return (double)(long long)fbx[ch * npix + p] * FX_UNIT;
-}
-
-// a pixel the resolve must not trust: its coarse magnitude reached FX_MAG_LIMIT (or is NaN), or a
-// channel sum lies in [2^61, 2^64) scaled (>= 2^17 in colour units; negative = wrapped)
-__device__ __forceinline__ bool fx_suspect(const unsigned long long* fbx, int64_t npix, int64_t p) {
-    bool bad = !(fx_mag(fbx, npix)[p] < FX_MAG_LIMIT);
-    for (int ch = 0; ch < 3; ++ch) bad |= (fbx[ch * npix + p] >> 61) != 0;
-    return bad;
-}
-
-__device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
-// Reserve `cnt` consecutive slots of the output shard for every active lane: one atomic per wave.
-// The exclusive prefix of the (small) per-lane counts is assembled from one ballot per bit, which
-// is exact in divergent code (inactive lanes contribute nothing).
-__device__ __forceinline__ uint32_t wave_reserve(uint32_t* ctr, uint32_t cnt) {
-    uint32_t total = 0, below = 0;
-    uint64_t any = __ballot(cnt != 0);
-    if (!any) return 0;
-    for (int b = 0; b < 8; ++b) {
-        uint64_t m = __ballot((cnt >> b) & 1u);
-        total += (uint32_t)__builtin_popcountll(m) << b;
-        below += lanes_below(m) << b;
-    }
-    uint32_t base = 0;
-#ifdef RT_ABL_NOATOMIC  // diagnostic build only: no counter traffic at all
-    return below + (total & 0u);
-#endif
-#ifdef RT_ABL_APPEND  // diagnostic build only: counts kept, slots not waited for (wrong images)
-    if (lanes_below(__ballot(1)) == 0) atomicAdd(ctr, total);
-    return ((blockIdx.x * 256u + threadIdx.x) * 2u + below % 2u) % 400000u;
-#endif
-    if (lanes_below(__ballot(1)) == 0) base = atomicAdd(ctr, total);  // first active lane
-    base = __builtin_amdgcn_readfirstlane(base);
-    return base + below;
-}
-
-// the exclusive prefix of `cnt` over the active lanes below this one (wave_reserve's `below`)
-__device__ __forceinline__ uint32_t wave_below(uint32_t cnt) {
-    uint32_t below = 0;
-    for (int b = 0; b < 8; ++b) below += lanes_below(__ballot((cnt >> b) & 1u)) << b;
-    return below;
-}
-
-// A pixel's colour summed in the thread that traces (some of) its samples, in one of two forms
-// sharing the same registers:
-//  * fixed point (P.fbx set, the default): every term -- depth 0 included -- rounded to a multiple of
-//    2^-FX_BITS and summed as an integer (unsigned: wrapping is defined), exactly fb_add's terms, plus
-//    fb_add's coarse magnitude (the f32 sum of |r| + |g| + |b| of the terms, independent of the sums).
-//    Integer sums do not depend on the order or grouping of the terms, so a pixel's samples may be
-//    split over any number of threads (sample groups, k_primary) or GPUs and the totals are the same
-//    bits.  A term of magnitude >= 2^17 (or NaN) is left out of the sums and shows in the magnitude
-//    (>= FX_MAG_LIMIT or NaN): the frame is then rendered again in f64.
-//  * f64 (option deterministic 0, or that fallback): the f64 sums, in the words' bits.
-struct PixAcc {
-    unsigned long long w[3] = {0ull, 0ull, 0ull};
-    float mag = 0.0f;
-
-    __device__ __forceinline__ void add(bool fx, d3 t) {
-        if (fx) {
-            const double m = (fabs(t.x) + fabs(t.y)) + fabs(t.z);
-            if (m < FX_MAX) {  // every |term| < 2^17: the conversions are in range (NaN fails too)
-                w[0] += (unsigned long long)__double2ll_rn(t.x * FX_SCALE);
-                w[1] += (unsigned long long)__double2ll_rn(t.y * FX_SCALE);
-                w[2] += (unsigned long long)__double2ll_rn(t.z * FX_SCALE);
-            }
-            mag += (float)m;
-        } else {
-            w[0] = (unsigned long long)__double_as_longlong(__longlong_as_double((long long)w[0]) + t.x);
-            w[1] = (unsigned long long)__double_as_longlong(__longlong_as_double((long long)w[1]) + t.y);
-            w[2] = (unsigned long long)__double_as_longlong(__longlong_as_double((long long)w[2]) + t.z);
-        }
-    }
-    __device__ __forceinline__ double value(bool fx, int k) const {
-        return fx ? (double)(long long)w[k] * FX_UNIT : __longlong_as_double((long long)w[k]);
-    }
-    // the pixel's fixed-point totals the resolve must not trust (fx_suspect's rule)
-    __device__ __forceinline__ bool suspect() const {
-        return !(mag < FX_MAG_LIMIT) || ((w[0] | w[1] | w[2]) >> 61) != 0;
-    }
-    // sum over the lanes l ^ off, off = 32, 16, .. >= lo (the sample groups of a pixel, k_primary):
-    // integer sums exactly; f64 sums pairwise, commutative, so every lane ends with the same value
-    __device__ __forceinline__ void reduce_lanes(bool fx, int lo) {
-        for (int off = 32; off >= lo; off >>= 1) {
-            for (int k = 0; k < 3; ++k) {
-                const unsigned long long o = __shfl_xor(w[k], off);
-                w[k] = fx ? w[k] + o
-                          : (unsigned long long)__double_as_longlong(__longlong_as_double((long long)w[k]) +
-                                                                     __longlong_as_double((long long)o));
-            }
-            mag += __shfl_xor(mag, off);
-        }
-    }
-};
-
-
-// Emitter of the GPU trace step: colour -> framebuffer atomics, children -> output queue shard.
-struct GpuEmit {
-    const TraceParams& P;
-    const Ray& r;
-    uint32_t shard;
-    uint32_t round;
-    uint32_t* shadow_acc;
-    PixAcc* acc;  // depth 0: the pixel's sums in the thread (no framebuffer atomics)
-
-    __device__ void local(d3 c) const {
-        if (acc) {
-            if (!is_zero(c)) acc->add(P.fbx != nullptr, mul(r.w, c));
-        } else {
-            fb_add(P.fb, P.fbx, P.flags, P.npix, r.pix, r.w, c);
-        }
-    }
-    __device__ void shadow(int n) const { *shadow_acc += (uint32_t)n; }
-    __device__ void store(uint32_t slot, const Child& c, uint32_t path) const {
-#if defined(RT_ABL_QSTORE) || defined(RT_ABL_NOATOMIC)  // diagnostic build only: no queue stores
-        if (c.o.x == 12345.678) P.flags[1] = path;
-        return;
-#endif
-        if (slot < (uint64_t)P.seg) {
-            queue_store(P.qout, (int64_t)shard * P.seg + slot, c.o, c.d, mul(r.w, c.w), r.pix,
-                        pack_meta(c.medium, meta_depth(r.meta) + 1, c.dfl), path);
-        } else {
-            atomicOr(&P.flags[1], RETRY_OVERFLOW);
-        }
-    }
-    __device__ void child(const Child& c) const {
-        uint32_t slot = wave_reserve(P.cnt_out + shard, 1u);
-        store(slot, c, child_path(r.path, c.slot, round));
-    }
-    // the fan-out child-major: the k-th children of the wave's lanes take consecutive slots, so every
-    // store of a child is one coalesced run (lane-major slots scattered each store over 64 lines)
-    __device__ void diffuse(const DiffuseGen& g, int mi) const {
-        const uint32_t cnt = (uint32_t)g.count;
-        const uint32_t base = wave_reserve(P.cnt_out + shard, cnt) - wave_below(cnt);
-        const auto& m = P.S.mat[mi];
-        uint32_t off = 0;
-        for (uint32_t k = 0;; ++k) {
-            const uint64_t mk = __ballot(cnt > k);
-            if (!mk) break;
-            if (cnt > k) {
-                Rng rng;
-                const uint32_t cpath = child_path(r.path, 0x100u + k, round);
-                rng.init(P.seed, key_pix(P, r.pix), cpath, 0xD1000000u | meta_depth(r.meta));
-                store(base + off + lanes_below(mk), diffuse_child(P.S, m, g, rng, k), cpath);
-            }
-            off += (uint32_t)__builtin_popcountll(mk);
-        }
-    }
-};
-
-__device__ __forceinline__ double mc_uniform(const TraceParams& P, const Ray& r, int cid, uint32_t round) {
-    if (!(P.S.col[cid].flags & SRT_CF_MC)) return 0.0;
-    Rng g;
-    g.init(P.seed, key_pix(P, r.pix), r.path, 0x3C000000u | (meta_depth(r.meta) << 8) | round);
-    return g.one();
-}
-
-// Uniforms for primary ray of sample s at local pixel p.
-__device__ __forceinline__ void primary_uniforms(const TraceParams& P, int s, uint32_t p, uint32_t gpix,
-                                                 double j[4]) {
-    if (P.jitter) {
-        const int64_t plane = P.jit_plane;
-        const double* base = P.jitter + (int64_t)s * 4 * plane + (P.jit_global ? gpix : p);
-        j[0] = base[0]; j[1] = base[plane];
-        // the lens-disk pair is read only by a thin-lens camera (pinhole: primary_ray skips it)
-        if (P.cam.lens_radius != 0.0) { j[2] = base[2 * plane]; j[3] = base[3 * plane]; }
-    } else {
-        Rng g;
-        g.init(P.seed, gpix, (uint32_t)(P.sample_base + s), 0xCA3E0000u);
-        g.two(j[0], j[1]);
-        g.two(j[2], j[3]);
-    }
-}
-
-// k_primary's split of primary_uniforms: the pixel-jitter pair (prefetched a sample ahead) and the
-// lens-disk pair (thin-lens cameras only), the same values
-__device__ __forceinline__ void primary_jitter(const TraceParams& P, int s, uint32_t p, uint32_t gpix, double j[2]) {
-#ifdef RT_ABL_JIT  // diagnostic build only: no jitter loads (wrong images; timing only)
-    j[0] = 0.5 + 1e-9 * (double)(s & 7);
-    j[1] = 0.5;
-    return;
-#endif
-    if (P.jitter) {
-        const int64_t plane = P.jit_plane;
-        const double* base = P.jitter + (int64_t)s * 4 * plane + (P.jit_global ? gpix : p);
-        j[0] = base[0];
-        j[1] = base[plane];
-    } else {
-        double j4[4];
-        primary_uniforms(P, s, p, gpix, j4);
-        j[0] = j4[0];
-        j[1] = j4[1];
-    }
-}
-__device__ __forceinline__ void lens_jitter(const TraceParams& P, int s, uint32_t p, uint32_t gpix, double j[4]) {
-    double j4[4] = {0.0, 0.0, 0.0, 0.0};
-    primary_uniforms(P, s, p, gpix, j4);
-    j[2] = j4[2];
-    j[3] = j4[3];
-}
-
-// an emitter whose child replaces the traced ray in place (Em::kInPlace)
-template <class Em, class = void>
-struct em_in_place : std::false_type {};
-template <class Em>
-struct em_in_place<Em, std::void_t<decltype(Em::kInPlace)>> : std::bool_constant<Em::kInPlace> {};
 
 // One trace step for one ray (all lanes of the wave call it; `active` masks the tail).
 // MATS: material types compiled into this instantiation (the host picks one covering the scene).
@@ -3371,658 +2990,8 @@ int srt_shade_level_inputs(srt_ctx* c, const srt_trace_args* a, const int32_t* c
     return trace_impl(c, a, collider, t, orient, st, kids, in, "srt_shade_level_inputs");
 }
 
-int srt_nearest(srt_ctx* c, const double* O, const double* D, int64_t n, double* t, int32_t* id, double* orient) {
-    if (!c || !O || !D) return fail(SRT_ERR_ARG, "null argument");
-    if (!c->has_scene) return fail(SRT_ERR_NOSCENE, "no scene uploaded");
-    if (n <= 0) return SRT_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    DevList bufs;
-    double *dO, *dD, *dt, *dor;
-    int32_t* did;
-    HIP_TRY(bufs.in(&dO, O, 3 * n));
-    HIP_TRY(bufs.in(&dD, D, 3 * n));
-    HIP_TRY(bufs.alloc(&dt, n));
-    HIP_TRY(bufs.alloc(&dor, n));
-    HIP_TRY(bufs.alloc(&did, n));
-    if (int rc = run_kernel(c, n, nullptr, nullptr, k_nearest, c->S, dO, dD, n, dt, did, dor)) return rc;
-    if (t) HIP_TRY(bufs.copy(t, dt, n));
-    if (id) HIP_TRY(bufs.copy(id, did, n));
-    if (orient) HIP_TRY(bufs.copy(orient, dor, n));
-    return SRT_OK;
-}
-
-int srt_intersect_collider(srt_ctx* c, const srt_collider* col, const double* O, const double* D, int64_t n,
-                           double* out) {
-    if (!c || !col || !O || !D || !out) return fail(SRT_ERR_ARG, "null argument");
-    if (col->type < 0 || col->type > 3) return fail(SRT_ERR_ARG, "bad collider type");
-    if (n <= 0) return SRT_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    DevList bufs;
-    double *dO, *dD, *dout;
-    srt_collider* dcol;
-    HIP_TRY(bufs.in(&dO, O, 3 * n));
-    HIP_TRY(bufs.in(&dD, D, 3 * n));
-    HIP_TRY(bufs.alloc(&dout, 2 * n));
-    HIP_TRY(bufs.in(&dcol, col, 1));
-    if (int rc = run_kernel(c, n, nullptr, nullptr, k_intersect_one, dcol, dO, dD, n, dout)) return rc;
-    HIP_TRY(bufs.copy(out, dout, 2 * n));
-    return SRT_OK;
-}
-
-int srt_collider_surface(srt_ctx* c, const srt_collider* col, const double* P, int64_t n, double* N, double* uv,
-                         int primitive_uv) {
-    if (!c || !col || !P || (!N && !uv)) return fail(SRT_ERR_ARG, "null argument");
-    if (col->type < 0 || col->type > 3) return fail(SRT_ERR_ARG, "bad collider type");
-    if (uv && col->type == SRT_TRIANGLE && !(col->flags & SRT_CF_VUV))
-        return fail(SRT_ERR_ARG, "Triangle uv is undefined in the reference (triangle.py:79-83)");
-    if (n <= 0) return SRT_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    DevList bufs;
-    srt_collider rec = *col;
-    if (!primitive_uv) rec.flags &= ~SRT_CF_UV_CROSS;  // the collider's own 4x3 cross coordinates
-    double *dP, *dN = nullptr, *duv = nullptr;
-    srt_collider* dcol;
-    HIP_TRY(bufs.in(&dP, P, 3 * n));
-    if (N) HIP_TRY(bufs.alloc(&dN, 3 * n));
-    if (uv) HIP_TRY(bufs.alloc(&duv, 2 * n));
-    HIP_TRY(bufs.in(&dcol, &rec, 1));
-    if (int rc = run_kernel(c, n, nullptr, nullptr, k_collider_surface, dcol, dP, n, dN, duv)) return rc;
-    if (N) HIP_TRY(bufs.copy(N, dN, 3 * n));
-    if (uv) HIP_TRY(bufs.copy(uv, duv, 2 * n));
-    return SRT_OK;
-}
-
-int srt_texture_lookup(srt_ctx* c, const srt_texture* tex, const uint8_t* texels, int64_t texel_bytes,
-                       const double* uv, int64_t n, double* rgb) {
-    if (!c || !tex || !texels || !uv || !rgb) return fail(SRT_ERR_ARG, "null argument");
-    if (tex->offset < 0 || tex->offset + tex->height * tex->width * tex->channels > texel_bytes)
-        return fail(SRT_ERR_ARG, "texture record outside the texel array");
-    if (n <= 0) return SRT_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    DevList bufs;
-    uint8_t* dtexels;
-    srt_texture* dtex;
-    double *duv, *drgb;
-    uint32_t* dflags;
-    HIP_TRY(bufs.in(&dtexels, texels, texel_bytes));
-    HIP_TRY(bufs.in(&dtex, tex, 1));
-    HIP_TRY(bufs.in(&duv, uv, 2 * n));
-    HIP_TRY(bufs.alloc(&drgb, 3 * n));
-    HIP_TRY(bufs.alloc(&dflags, 1));
-    HIP_TRY(hipMemset(dflags, 0, 4));
-    SceneView S{};
-    S.tex = (const RT_RO srt_texture*)dtex;
-    S.texels = (const RT_RO uint8_t*)dtexels;
-    S.ntex = 1;
-    int flag_rc = SRT_OK;
-    if (int rc = run_kernel(c, n, dflags, &flag_rc, k_texture_lookup, S, duv, n, drgb, dflags)) return rc;
-    HIP_TRY(bufs.copy(rgb, drgb, 3 * n));
-    return flag_rc;
-}
-
-int srt_material_normal(srt_ctx* c, const srt_collider* col, const srt_texture* normalmap, const uint8_t* texels,
-                        int64_t texel_bytes, const double* P, const double* orient, int64_t n, double* N) {
-    if (!c || !col || !P || !orient || !N) return fail(SRT_ERR_ARG, "null argument");
-    if (col->type < 0 || col->type > 3) return fail(SRT_ERR_ARG, "bad collider type");
-    if (normalmap) {
-        if (!texels || normalmap->offset < 0 || normalmap->channels < 3 || normalmap->channel0 < 0 ||
-            normalmap->channel0 + 3 > normalmap->channels ||
-            normalmap->offset + (int64_t)normalmap->height * normalmap->width * normalmap->channels > texel_bytes)
-            return fail(SRT_ERR_ARG, "normal-map record outside the texel array");
-        if (col->type != SRT_PLANE && col->type != SRT_CUBOID)
-            return fail(SRT_ERR_ARG, "a normal map needs the collider's inverse_basis_matrix (Plane, Cuboid)");
-    }
-    if (n <= 0) return SRT_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    DevList bufs;
-    srt_material mrec{};
-    mrec.type = SRT_GLOSSY;
-    mrec.tex = mrec.tex_aux0 = mrec.tex_aux1 = -1;
-    mrec.normalmap = normalmap ? 0 : -1;
-    srt_collider* dcol;
-    srt_material* dmat;
-    srt_texture* dtex = nullptr;
-    uint8_t* dtexels = nullptr;
-    double *dP, *dor, *dN;
-    uint32_t* dflags;
-    HIP_TRY(bufs.in(&dcol, col, 1));
-    HIP_TRY(bufs.in(&dmat, &mrec, 1));
-    HIP_TRY(bufs.in(&dP, P, 3 * n));
-    HIP_TRY(bufs.in(&dor, orient, n));
-    HIP_TRY(bufs.alloc(&dN, 3 * n));
-    HIP_TRY(bufs.alloc(&dflags, 1));
-    HIP_TRY(hipMemset(dflags, 0, 4));
-    SceneView S{};
-    if (normalmap) {
-        HIP_TRY(bufs.in(&dtex, normalmap, 1));
-        HIP_TRY(bufs.in(&dtexels, texels, texel_bytes));
-        S.tex = (const RT_RO srt_texture*)dtex;
-        S.texels = (const RT_RO uint8_t*)dtexels;
-        S.ntex = 1;
-    }
-    int flag_rc = SRT_OK;
-    if (int rc = run_kernel(c, n, dflags, &flag_rc, k_material_normal, S, dcol, dmat, dP, dor, n, dN, dflags)) return rc;
-    HIP_TRY(bufs.copy(N, dN, 3 * n));
-    return flag_rc;
-}
-
-int srt_primary_rays(srt_ctx* c, const srt_camera* cam, const double* J, double* O, double* D) {
-    if (!c || !cam || !J || !O || !D) return fail(SRT_ERR_ARG, "null argument");
-    HIP_TRY(hipSetDevice(c->device));
-    DevList bufs;
-    const int64_t n = (int64_t)cam->width * cam->height;
-    double *dJ, *dO, *dD, *xs, *ys;
-    HIP_TRY(bufs.in(&dJ, J, 4 * n));
-    HIP_TRY(bufs.alloc(&dO, 3 * n));
-    HIP_TRY(bufs.alloc(&dD, 3 * n));
-    HIP_TRY(bufs.in(&xs, cam->xs, cam->width));
-    HIP_TRY(bufs.in(&ys, cam->ys, cam->height));
-    srt_camera k = *cam;
-    k.xs = xs;
-    k.ys = ys;
-    if (int rc = run_kernel(c, n, nullptr, nullptr, k_primary_rays, k, dJ, n, dO, dD)) return rc;
-    HIP_TRY(bufs.copy(O, dO, 3 * n));
-    HIP_TRY(bufs.copy(D, dD, 3 * n));
-    return SRT_OK;
-}
-
-// ---- denoising (rt_denoise.h) -----------------------------------------------------------------------
-int srt_render_aovs(srt_ctx* c, const srt_camera* cam, srt_aov_out* out) {
-    if (!c || !cam || !out) return fail(SRT_ERR_ARG, "null argument");
-    if (!c->has_scene) return fail(SRT_ERR_NOSCENE, "no scene uploaded");
-    if (cam->width <= 0 || cam->height <= 0 || !cam->xs || !cam->ys) return fail(SRT_ERR_ARG, "bad camera");
-    if (std::find(c->col_hit_albedo.begin(), c->col_hit_albedo.end(), 1) != c->col_hit_albedo.end())
-        return fail(SRT_ERR_ARG, "srt_render_aovs: the scene holds an SRT_MF_HIT_ALBEDO material (a user texture: "
-                                 "its albedo is not known to the device)");
-    HIP_TRY(hipSetDevice(c->device));
-    DevList bufs;
-    const int64_t n = (int64_t)cam->width * cam->height;
-    AovOut d{};
-    if (out->hit_id) HIP_TRY(bufs.alloc(&d.hit_id, n));
-    if (out->depth) HIP_TRY(bufs.alloc(&d.depth, n));
-    if (out->position) HIP_TRY(bufs.alloc(&d.position, 3 * n));
-    if (out->normal) HIP_TRY(bufs.alloc(&d.normal, 3 * n));
-    if (out->albedo) HIP_TRY(bufs.alloc(&d.albedo, 3 * n));
-    double *xs, *ys;
-    uint32_t* dflags;
-    HIP_TRY(bufs.in(&xs, cam->xs, cam->width));
-    HIP_TRY(bufs.in(&ys, cam->ys, cam->height));
-    HIP_TRY(bufs.alloc(&dflags, 1));
-    HIP_TRY(hipMemset(dflags, 0, 4));
-    srt_camera k = *cam;
-    k.xs = xs;
-    k.ys = ys;
-    SceneView S = c->S;
-    S.nlut_lds = 0;  // (k_aov stages no texture tables in LDS: it reads them from the texture records)
-    EventList ev;
-    HIP_TRY(ev.create(2));
-    hipStream_t st = c->f->stream;
-    HIP_TRY(hipEventRecord(ev.e[0], st));
-    hipLaunchKernelGGL(k_aov, dim3(grid_for(n, c->max_blocks)), dim3(DN_BLOCK), 0, st, S, k, d, dflags);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev.e[1], st));
-    HIP_TRY(hipStreamSynchronize(st));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-    out->ms_kernel = ms;
-    uint32_t flags = 0;
-    HIP_TRY(hipMemcpy(&flags, dflags, 4, hipMemcpyDefault));
-    if (int rc = check_flags(flags)) return rc;
-    if (out->hit_id) HIP_TRY(bufs.copy(out->hit_id, d.hit_id, n));
-    if (out->depth) HIP_TRY(bufs.copy(out->depth, d.depth, n));
-    if (out->position) HIP_TRY(bufs.copy(out->position, d.position, 3 * n));
-    if (out->normal) HIP_TRY(bufs.copy(out->normal, d.normal, 3 * n));
-    if (out->albedo) HIP_TRY(bufs.copy(out->albedo, d.albedo, 3 * n));
-    return SRT_OK;
-}
-
-int srt_denoise(srt_ctx* c, int32_t width, int32_t height, const srt_denoise_args* a) {
-    if (!c || !a) return fail(SRT_ERR_ARG, "null argument");
-    if (width <= 0 || height <= 0) return fail(SRT_ERR_ARG, "srt_denoise: non-positive image size");
-    if (!a->rgb || !a->normal || !a->albedo || !a->position || !a->depth)
-        return fail(SRT_ERR_ARG, "srt_denoise: NULL colour or guide array");
-    if (a->levels < 0 || a->levels > SRT_DENOISE_MAX_LEVELS) return fail(SRT_ERR_ARG, "srt_denoise: levels outside 0..8");
-    if (!(a->sigma_color > 0.0) || !(a->sigma_normal > 0.0) || !(a->sigma_albedo > 0.0) || !(a->sigma_plane > 0.0))
-        return fail(SRT_ERR_ARG, "srt_denoise: sigmas must be positive");
-    if (a->flags & ~SRT_DENOISE_RGBX) return fail(SRT_ERR_ARG, "srt_denoise: unknown flag");
-    if (!a->out_rgb && !a->out_srgb8) return fail(SRT_ERR_ARG, "srt_denoise: no output");
-    HIP_TRY(hipSetDevice(c->device));
-    DevList bufs;
-    const int64_t n = (int64_t)width * height;
-    AtrousPlanes G{};
-    G.npix = n;
-    G.W = width;
-    HIP_TRY(stage_in(bufs, a->rgb, 3 * n, &G.rgb));
-    HIP_TRY(stage_in(bufs, a->normal, 3 * n, &G.normal));
-    HIP_TRY(stage_in(bufs, a->albedo, 3 * n, &G.albedo));
-    HIP_TRY(stage_in(bufs, a->position, 3 * n, &G.position));
-    HIP_TRY(stage_in(bufs, a->depth, n, &G.depth));
-    double* pong[2] = {nullptr, nullptr};  // the levels' colour buffers
-    for (int k = 0; k < std::min(a->levels, 2); ++k) HIP_TRY(bufs.alloc(&pong[k], 3 * n));
-    const bool rgbx = (a->flags & SRT_DENOISE_RGBX) != 0;
-    const int64_t u8_bytes = n * (rgbx ? 4 : 3);
-    uint8_t* du8 = nullptr;
-    if (a->out_srgb8) {
-        if (is_device_ptr(a->out_srgb8))
-            du8 = a->out_srgb8;
-        else
-            HIP_TRY(bufs.alloc(&du8, u8_bytes));
-    }
-    EventList ev;
-    if (a->ms_levels) HIP_TRY(ev.create(a->levels + 2));
-    hipStream_t st = c->f->stream;
-    const int64_t segs = ((int64_t)width + 63) / 64;
-    const int grid = grid_for(segs * height * 64, c->max_blocks);
-    if (a->ms_levels) HIP_TRY(hipEventRecord(ev.e[0], st));
-    for (int l = 0; l < a->levels; ++l) {
-        AtrousLevel K{};
-        K.W = width, K.H = height, K.step = 1 << l;
-        const double sc = a->sigma_color * ldexp(1.0, -l);
-        K.sc2 = sc * sc;
-        K.sn2 = a->sigma_normal * a->sigma_normal;
-        K.sa2 = a->sigma_albedo * a->sigma_albedo;
-        K.sp2 = a->sigma_plane * a->sigma_plane;
-        hipLaunchKernelGGL(k_atrous, dim3(grid), dim3(DN_BLOCK), 0, st, G, K, pong[l & 1]);
-        HIP_TRY(hipGetLastError());
-        if (a->ms_levels) HIP_TRY(hipEventRecord(ev.e[(size_t)l + 1], st));
-        G.rgb = pong[l & 1];
-    }
-    if (du8) {
-        hipLaunchKernelGGL(k_denoise_resolve, dim3(grid_for(n, c->max_blocks)), dim3(DN_BLOCK), 0, st, G.rgb, n, du8,
-                           rgbx ? 1 : 0);
-        HIP_TRY(hipGetLastError());
-    }
-    if (a->ms_levels) HIP_TRY(hipEventRecord(ev.e[(size_t)a->levels + 1], st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (int l = 0; l <= a->levels && a->ms_levels; ++l) {
-        // each level, then the whole chain (first launch to the end of the resolve)
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ev.e[l < a->levels ? (size_t)l : 0], ev.e[(size_t)l + 1]));
-        a->ms_levels[l] = ms;
-    }
-    if (a->out_rgb && a->out_rgb != G.rgb) HIP_TRY(bufs.copy(a->out_rgb, G.rgb, 3 * n));
-    if (a->out_srgb8 && du8 != a->out_srgb8) HIP_TRY(bufs.copy(a->out_srgb8, (const uint8_t*)du8, u8_bytes));
-    return SRT_OK;
-}
-
-int srt_device_alloc(srt_ctx* c, int64_t bytes, void** out) {
-    if (!c || !out || bytes <= 0) return fail(SRT_ERR_ARG, "bad argument");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMalloc(out, (size_t)bytes));
-    return SRT_OK;
-}
-
-int srt_device_free(srt_ctx* c, void* p) {
-    if (!c) return fail(SRT_ERR_ARG, "null ctx");
-    HIP_TRY(hipSetDevice(c->device));
-    if (p) HIP_TRY(hipFree(p));
-    return SRT_OK;
-}
-
-int srt_memcpy(srt_ctx* c, void* dst, const void* src, int64_t bytes) {
-    if (!c || !dst || !src || bytes < 0) return fail(SRT_ERR_ARG, "bad argument");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpy(dst, src, (size_t)bytes, hipMemcpyDefault));
-    return SRT_OK;
-}
-
-int srt_mt19937_uniforms(srt_ctx* c, const uint32_t* key, int32_t pos, int64_t n_out, int64_t n_skip, double* out,
-                         uint32_t* key_out, int32_t* pos_out) {
-    if (!c || !key || !key_out || !pos_out || (n_out > 0 && !out)) return fail(SRT_ERR_ARG, "null argument");
-    c->pf.valid = false;  // (generates from the stream state a prefetch assumed)
-    if (pos < 0 || pos > rtmt::N || n_out < 0 || n_skip < 0) return fail(SRT_ERR_ARG, "bad position or count");
-    if (is_device_ptr(key) || is_device_ptr(key_out)) return fail(SRT_ERR_ARG, "key and key_out are host arrays");
-    if (n_out + n_skip == 0) {
-        memcpy(key_out, key, rtmt::N * 4);
-        *pos_out = pos;
-        return SRT_OK;
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = finish_async(c, nullptr);  // frames in flight may use the generator's scratch
-    if (rc) return rc;
-    if ((rc = mt_ensure(c))) return rc;
-    double* dst = out;
-    const bool host_out = n_out > 0 && !is_device_ptr(out);
-    if (host_out) {
-        if ((rc = c->mt_out.ensure(n_out))) return rc;
-        dst = c->mt_out;
-    }
-    hipStream_t st = c->f->stream;
-    HIP_TRY(hipMemcpyAsync(mt_key0(c), key, rtmt::N * 4, hipMemcpyHostToDevice, st));
-    int final_pos = 0;
-    if ((rc = mt_win_ensure(c, *c->f, (int64_t)rtmt::SEGS * rtmt::N))) return rc;
-    if ((rc = mt_launch(c, st, c->f->mt_win, mt_key0(c), pos, n_out, n_skip, dst, &final_pos))) return rc;
-    if (host_out) HIP_TRY(hipMemcpyAsync(out, dst, (size_t)n_out * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(key_out, mt_dump(c), rtmt::N * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *pos_out = final_pos;
-    return SRT_OK;
-}
-
-// ---- multi-GPU ------------------------------------------------------------------------------
-int srt_comm_unique_id(uint8_t* id) {
-    if (!id) return fail(SRT_ERR_ARG, "null id");
-    static_assert(sizeof(ncclUniqueId) == SRT_COMM_ID_BYTES, "ncclUniqueId size");
-    ncclUniqueId u;
-    NCCL_TRY(ncclGetUniqueId(&u));
-    memcpy(id, &u, sizeof(u));
-    return SRT_OK;
-}
-
-int srt_comm_init(srt_ctx* c, int nranks, int rank, const uint8_t* id) {
-    if (!c || !id || nranks < 1 || nranks > MAX_RANKS || rank < 0 || rank >= nranks)
-        return fail(SRT_ERR_ARG, "bad communicator arguments");
-    if (c->comm) return fail(SRT_ERR_ARG, "context already has a communicator");
-    HIP_TRY(hipSetDevice(c->device));
-    ncclUniqueId u;
-    memcpy(&u, id, sizeof(u));
-    NCCL_TRY(ncclCommInitRank(&c->comm, nranks, u, rank));
-    c->nranks = nranks;
-    c->rank = rank;
-    return SRT_OK;
-}
-
-int srt_comm_init_all(int ndev, const int* devs, srt_ctx** ctxs) {
-    if (ndev < 1 || ndev > MAX_RANKS || !devs || !ctxs) return fail(SRT_ERR_ARG, "bad device list");
-    for (int q = 0; q < ndev; ++q) ctxs[q] = nullptr;
-    for (int q = 0; q < ndev; ++q) {
-        int rc = srt_create(devs[q], &ctxs[q]);
-        if (rc) {
-            for (int k = 0; k < q; ++k) srt_destroy(ctxs[k]);
-            return rc;
-        }
-    }
-    std::vector<ncclComm_t> comms(ndev);
-    ncclResult_t r = ncclCommInitAll(comms.data(), ndev, devs);
-    if (r != ncclSuccess) {
-        for (int k = 0; k < ndev; ++k) srt_destroy(ctxs[k]);
-        return fail(SRT_ERR_HIP, std::string("ncclCommInitAll: ") + ncclGetErrorString(r));
-    }
-    for (int q = 0; q < ndev; ++q) {
-        ctxs[q]->comm = comms[q];
-        ctxs[q]->nranks = ndev;
-        ctxs[q]->rank = q;
-    }
-    return SRT_OK;
-}
-
-int srt_comm_rank(srt_ctx* c, int* nranks, int* rank) {
-    if (!c || !nranks || !rank) return fail(SRT_ERR_ARG, "null argument");
-    *nranks = c->nranks;
-    *rank = c->rank;
-    return SRT_OK;
-}
-
 }  // extern "C"
 
-// The gathers of all the group's contexts posted in one RCCL group, then the frame assembled on rank 0
-static int gather_group(srt_ctx** ctxs, int n) {
-    int rc = SRT_OK;
-    if (n > 1) {
-        ncclResult_t r = ncclGroupStart();
-        for (int q = 0; q < n && !rc && r == ncclSuccess; ++q) {
-            (void)hipSetDevice(ctxs[q]->device);
-            rc = gather_post(ctxs[q]);
-        }
-        ncclResult_t r2 = ncclGroupEnd();
-        if (!rc && (r != ncclSuccess || r2 != ncclSuccess))
-            rc = fail(SRT_ERR_HIP, std::string("RCCL group gather: ") + ncclGetErrorString(r != ncclSuccess ? r : r2));
-    }
-    if (!rc) {
-        (void)hipSetDevice(ctxs[0]->device);
-        rc = gather_finish(ctxs[0]);
-    }
-    return rc;
-}
-
-// srt_render_finish on every context (whatever `rc` the frame had so far: no rank is left with frames
-// in flight); `sum`: rank 0's stats with the ray counts of all ranks.  Returns the first error.
-static int finish_group(srt_ctx** ctxs, int n, srt_stats& sum, int rc) {
-    for (int q = 0; q < n; ++q) {
-        srt_stats sq{};
-        const int r = srt_render_finish(ctxs[q], &sq);
-        if (!rc) rc = r;
-        if (q == 0) {
-            sum = sq;
-        } else {
-            for (int d = 0; d < SRT_MAX_DEPTHS; ++d) sum.rays_per_depth[d] += sq.rays_per_depth[d];
-            sum.total_rays += sq.total_rays;
-            sum.shadow_rays += sq.shadow_rays;
-            sum.n_depths = std::max(sum.n_depths, sq.n_depths);
-        }
-    }
-    return rc;
-}
-
-static int render_group_once(srt_ctx** ctxs, int n, const srt_camera* cam, const srt_render_args* a, srt_stats* st) {
-    const bool want_rgb = a->out_rgb != nullptr;
-    int rc = SRT_OK;
-    srt_render_args aq = *a;
-    aq.flags = SRT_RENDER_ASYNC | SRT_RENDER_SHARDED | (want_rgb ? SRT_RENDER_GATHER_RGB : (a->flags & SRT_RENDER_RGB_LOCAL));
-    aq.out_rgb = nullptr;  // rank 0 assembles into its slot buffers; copied to the caller's below
-    aq.out_srgb8 = nullptr;
-    for (int q = 0; q < n && !rc; ++q) {
-        if ((rc = finish_async(ctxs[q], nullptr))) break;
-        ctxs[q]->defer_gather = true;
-        rc = srt_render(ctxs[q], cam, &aq, nullptr);
-    }
-    FrameSlot* f0 = ctxs[0]->f;
-    if (!rc) rc = gather_group(ctxs, n);
-    for (int q = 0; q < n; ++q) ctxs[q]->defer_gather = false;
-    srt_stats sum{};
-    rc = finish_group(ctxs, n, sum, rc);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctxs[0]->device));
-    const int64_t np = (int64_t)cam->width * cam->height;
-    if (a->out_srgb8) HIP_TRY(hipMemcpy(a->out_srgb8, f0->full_u8, (size_t)3 * np, hipMemcpyDefault));
-    if (want_rgb) HIP_TRY(hipMemcpy(a->out_rgb, f0->full_rgb, (size_t)3 * np * 8, hipMemcpyDefault));
-    if (st) *st = sum;
-    return SRT_OK;
-}
-
-// A pipelined group frame (SRT_RENDER_ASYNC): every context queues its shard (asynchronous
-// srt_render, SRT_RENDER_SHARDED), the uint8 tiles' RCCL gather is posted for all of them in one
-// group, rank 0 assembles the frame and copies it to the caller's out_srgb8 (pinned host memory or
-// device memory of rank 0); the linear RGB goes to out_rgb (pinned host memory visible to every
-// context, srt_host_alloc) either gathered to rank 0 or, with SRT_RENDER_RGB_ROWS, as every rank's
-// rows over its own PCIe link.  Nothing waits: srt_render_group_finish checks every context.
-static int render_group_async(srt_ctx** ctxs, int n, const srt_camera* cam, const srt_render_args* a) {
-    srt_render_args aq = *a;
-    const bool rows = (a->flags & SRT_RENDER_RGB_ROWS) != 0;
-    aq.flags = SRT_RENDER_ASYNC | SRT_RENDER_SHARDED | (a->flags & SRT_RENDER_RGB_LOCAL) |
-               (rows ? SRT_RENDER_RGB_ROWS : (a->out_rgb ? SRT_RENDER_GATHER_RGB : 0));
-    int rc = SRT_OK;
-    int queued = 0;
-    for (int q = 0; q < n && !rc; ++q) {
-        aq.out_srgb8 = q == 0 ? a->out_srgb8 : nullptr;
-        aq.out_rgb = (rows || q == 0) ? a->out_rgb : nullptr;
-        ctxs[q]->defer_gather = true;
-        rc = srt_render(ctxs[q], cam, &aq, nullptr);
-        if (!rc) ++queued;
-    }
-    if (!rc) rc = gather_group(ctxs, n);
-    for (int q = 0; q < n; ++q) ctxs[q]->defer_gather = false;
-    if (rc && queued < n) {
-        // a context refused the frame: the others' shards are queued without the gather; wait for them
-        // (their frames are dropped) so that no rank is left a send without its receive
-        for (int q = 0; q < queued; ++q) (void)srt_render_finish(ctxs[q], nullptr);
-    }
-    return rc;
-}
-
-extern "C" {
-
-int srt_render_group(srt_ctx** ctxs, int n, const srt_camera* cam, const srt_render_args* a, srt_stats* st) {
-    if (!ctxs || n < 1 || !cam || !a) return fail(SRT_ERR_ARG, "null argument");
-    for (int q = 0; q < n; ++q)
-        if (!ctxs[q] || ctxs[q]->nranks != n || ctxs[q]->rank != q)
-            return fail(SRT_ERR_ARG, "contexts must be the ranks 0..n-1 of one srt_comm_init_all group");
-    for (int q = 0; q < n; ++q) ctxs[q]->pf.valid = false;
-    for (int q = 0; q < n; ++q)
-        if (ctxs[q]->has_scene && ctxs[q]->needs_inputs) return refuse_inputs_scene("srt_render_group");
-    if (a->jitter) return fail(SRT_ERR_ARG, "a group frame draws its jitter on the devices (mt or Philox)");
-    if (a->out_hit_id) return fail(SRT_ERR_ARG, "hit ids of a sharded frame are not gathered");
-    if (a->flags & ~(SRT_RENDER_ASYNC | SRT_RENDER_RGB_ROWS | SRT_RENDER_RGB_LOCAL))
-        return fail(SRT_ERR_ARG, "group flags: ASYNC, RGB_ROWS, RGB_LOCAL");
-    if ((a->flags & SRT_RENDER_RGB_LOCAL) && (a->out_rgb || (a->flags & SRT_RENDER_RGB_ROWS)))
-        return fail(SRT_ERR_ARG, "SRT_RENDER_RGB_LOCAL needs out_rgb NULL and no SRT_RENDER_RGB_ROWS");
-    if (a->flags & SRT_RENDER_ASYNC) return render_group_async(ctxs, n, cam, a);
-    // A frame whose passes overflowed a queue/ring, met a chain-mode tie or left the fixed-point range
-    // is rendered again on every context (the gather pairs the ranks' tiles), from the same numpy
-    // state, as the synchronous single-GPU path does; the contexts already grew their queues or
-    // dropped chain mode / fixed-point sums in finish_async.
-    srt_mt_state mt0{};
-    if (a->mt) mt0 = *a->mt;
-    int rc = SRT_OK;
-    for (int attempt = 0;; ++attempt) {
-        if (a->mt) *a->mt = mt0;
-        // (a flag left by an earlier frame must not make a failure of this one look retryable)
-        for (int q = 0; q < n; ++q) ctxs[q]->retry_frame = false;
-        rc = render_group_once(ctxs, n, cam, a, st);
-        bool again = false;
-        for (int q = 0; q < n; ++q) again |= ctxs[q]->retry_frame;
-        if (rc == SRT_OK && st) st->retries += attempt;  // frames rendered again, as srt_render counts them
-        if (rc == SRT_OK || !again || attempt >= 8) return rc;
-    }
-}
-
-
-int srt_render_group_finish(srt_ctx** ctxs, int n, srt_stats* st) {
-    if (!ctxs || n < 1) return fail(SRT_ERR_ARG, "null argument");
-    srt_stats sum{};
-    const int rc = finish_group(ctxs, n, sum, SRT_OK);
-    if (st && !rc) *st = sum;
-    return rc;
-}
-
-int srt_comm_allreduce(srt_ctx* c, double* vals, int n, int op) {
-    if (!c || !vals || n < 1 || n > 64 || op < 0 || op > 1) return fail(SRT_ERR_ARG, "bad allreduce arguments");
-    if (c->nranks == 1 || !c->comm) return SRT_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = finish_async(c, nullptr);
-    if (rc) return rc;
-    if (!c->red) HIP_TRY(dalloc(&c->red, 64));
-    hipStream_t st = c->f->stream;
-    HIP_TRY(hipMemcpyAsync(c->red, vals, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    NCCL_TRY(ncclAllReduce(c->red, c->red, (size_t)n, ncclFloat64, op == 0 ? ncclSum : ncclMax, c->comm, st));
-    HIP_TRY(hipMemcpyAsync(vals, c->red, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return SRT_OK;
-}
-
-int srt_comm_barrier(srt_ctx* c) {
-    double v = 0.0;
-    return srt_comm_allreduce(c, &v, 1, 0);
-}
-
-// (hipHostMalloc places the buffer on the GPU's NUMA node: tools/pcie_probe.py, 56 GB/s either way
-// the calling process is pinned)
-int srt_host_alloc(srt_ctx* c, int64_t bytes, void** out) {
-    if (!c || !out || bytes <= 0) return fail(SRT_ERR_ARG, "bad argument");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipHostMalloc(out, (size_t)bytes, hipHostMallocPortable));  // (pinned for every context's device)
-    return SRT_OK;
-}
-
-int srt_host_register(srt_ctx* c, void* p, int64_t bytes) {
-    if (!c || !p || bytes <= 0) return fail(SRT_ERR_ARG, "null ctx/pointer or bad size");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipHostRegister(p, (size_t)bytes, hipHostRegisterPortable));
-    return SRT_OK;
-}
-
-int srt_host_unregister(srt_ctx* c, void* p) {
-    if (!c || !p) return fail(SRT_ERR_ARG, "null ctx/pointer");
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = finish_async(c, nullptr);  // frames in flight may still write into it
-    if (rc) return rc;
-    HIP_TRY(hipHostUnregister(p));
-    return SRT_OK;
-}
-
-int srt_host_free(srt_ctx* c, void* p) {
-    if (!c) return fail(SRT_ERR_ARG, "null ctx");
-    if (p) HIP_TRY(hipHostFree(p));
-    return SRT_OK;
-}
-
-#ifdef RT_PROF
-// diagnostic build only: section counters of rt_device.h (64 words: 32 cycle sums, 32 counts)
-int srt_debug_prof(srt_ctx* c, unsigned long long* out, int reset) {
-    if (!c || !out) return fail(SRT_ERR_ARG, "null argument");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->f->stream));
-    HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_rt_prof), sizeof(unsigned long long) * 64));
-    if (reset) {
-        unsigned long long z[64] = {};
-        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_rt_prof), z, sizeof(z)));
-    }
-    return SRT_OK;
-}
-#endif
-
-int srt_debug_lean_launches(srt_ctx* c, int64_t* launches) {
-    if (!c || !launches) return fail(SRT_ERR_ARG, "null argument");
-    *launches = c->lean_launches;
-    return SRT_OK;
-}
-
-int srt_debug_lane_stats(srt_ctx* c, int mode, int64_t* out, int n) {
-    if (!c) return fail(SRT_ERR_ARG, "null ctx");
-    if (mode != 0 && mode != 1) return fail(SRT_ERR_ARG, "lane stats mode: 1 start, 0 read and stop");
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = finish_async(c, nullptr);  // (the frames in flight were queued with the old pointer)
-    if (rc) return rc;
-    const size_t bytes = (size_t)SRT_MAX_DEPTHS * 2 * sizeof(unsigned long long);
-    if (mode == 1) {
-        if (!c->lane_stats) HIP_TRY(dalloc(&c->lane_stats, SRT_MAX_DEPTHS * 2));
-        HIP_TRY(hipMemset(c->lane_stats, 0, bytes));
-        return SRT_OK;
-    }
-    if (!out || n < 0 || n > SRT_MAX_DEPTHS) return fail(SRT_ERR_ARG, "lane stats: out[n][2], n <= SRT_MAX_DEPTHS");
-    if (!c->lane_stats) return fail(SRT_ERR_ARG, "lane stats were not started");
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, c->lane_stats, (size_t)n * 2 * sizeof(int64_t), hipMemcpyDeviceToHost));
-    HIP_TRY(c->lane_stats.reset());
-    return SRT_OK;
-}
-
-int srt_debug_prefetch_counts(srt_ctx* c, int64_t* used, int64_t* queued) {
-    if (!c || !used || !queued) return fail(SRT_ERR_ARG, "null argument");
-    *used = c->pf_used;
-    *queued = c->pf_queued;
-    return SRT_OK;
-}
-
-int srt_debug_mt_residue(srt_ctx* c, int64_t* nonzero_words) {
-    if (!c || !nonzero_words) return fail(SRT_ERR_ARG, "null argument");
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = finish_async(c, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    int64_t nz = 0;
-    std::vector<uint32_t> h;
-    auto count = [&](const uint32_t* d, int64_t words) -> int {
-        h.resize((size_t)words);
-        HIP_TRY(hipMemcpy(h.data(), d, (size_t)words * 4, hipMemcpyDeviceToHost));
-        for (uint32_t w : h) nz += w != 0u;
-        return SRT_OK;
-    };
-    // (window 0 of a table holds a copy of the key, written by a plain store at every generation that
-    // jumps -- never an XOR target -- and left there when no segment starts at the key: not counted)
-    for (FrameSlot& f : c->slots)
-        if (f.mt_win && f.mt_win.cap > rtmt::N && (rc = count(f.mt_win + rtmt::N, f.mt_win.cap - rtmt::N))) return rc;
-    if (c->mt && (rc = count(mt_end_acc(c), rtmt::N + 1))) return rc;
-    *nonzero_words = nz;
-    return SRT_OK;
-}
-
-int srt_synchronize(srt_ctx* c) {
-    if (!c) return fail(SRT_ERR_ARG, "null ctx");
-    HIP_TRY(hipSetDevice(c->device));
-    for (FrameSlot& f : c->slots)
-        if (f.stream) HIP_TRY(hipStreamSynchronize(f.stream));
-    return SRT_OK;
-}
-
-}  // extern "C"
+#include "rt_api_entry.h"
+#include "rt_api_group.h"
+#include "rt_api_misc.h"

@@ -138,7 +138,7 @@ RT_MT_HD bool dumps(int s, int64_t d) {
 // sparse (~135 terms), so a reduction XORs each high 64-bit chunk back at the few term offsets.
 // A frame of a fixed shape consumes a fixed number of words, so the window at the end of frame k
 // (the next frame's key) is one jump from frame k's key: the pipelined generator of frame k+1 need
-// not wait for frame k's whole generation (rt_kernels.hip, k_mt_jump end block).
+// not wait for frame k's whole generation (rt_mt_kernel.h, k_mt_jump end block).
 constexpr int PW = 312;  // 64-bit words of a reduced polynomial (19968 bits >= 19937)
 struct Gf2 {
     uint64_t w[2 * PW];  // products before reduction

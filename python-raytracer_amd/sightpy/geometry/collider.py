@@ -4,7 +4,7 @@
 misses.  `get_Normal(hit)` / `get_uv(hit)` evaluate the collider's normal and surface
 coordinates at `hit.point` (sphere.py:54-64, plane.py:98-105, cuboid.py:142-187,
 triangle.py:85-86).  Every one runs on the GPU (`srt_intersect_collider`, `srt_collider_surface`
-in `csrc/rt_kernels.hip`); subclasses only describe their parameters (lowered by `_lower.py`).
+in `csrc/rt_api_entry.h`); subclasses only describe their parameters (lowered by `_lower.py`).
 """
 from ..utils.vector3 import vec3
 

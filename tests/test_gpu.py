@@ -487,7 +487,7 @@ def test_gpu_colour_beyond_fixed_point_range_falls_back_to_f64_sums():
 
 def test_gpu_fixed_point_sums_near_wrap_fall_back_to_f64_sums():
     """Every contribution below the per-term limit (2^17), but a pixel's reflected contributions
-    summing past the coarse magnitude limit (rt_kernels.hip FX_MAG_LIMIT, the guard against a
+    summing past the coarse magnitude limit (rt_trace_common.h FX_MAG_LIMIT, the guard against a
     fixed-point sum wrapping): the frame is rendered again with f64 atomics and matches the oracle."""
     from sightpy import Emissive, Sphere, rgb, vec3
 

@@ -11,7 +11,7 @@ map) -- through the C ABI, and compares it with the oracle on those rows:
 One sample per pixel (the oracle takes ~10-40 s per shard); the per-sample work is what spp
 multiplies.  Bar (north_star): primary hit ids exact, per-depth ray counts equal, linear RGB within
 1e-5 relative -- checked with NO absolute floor on every value above 1e-9 (the fixed-point
-framebuffer sums quantise each term to 2^-44, rt_kernels.hip fx_add), and within 1e-14 absolute
+framebuffer sums quantise each term to 2^-44, rt_trace_common.h fx_add), and within 1e-14 absolute
 below it.
 """
 import numpy as np
