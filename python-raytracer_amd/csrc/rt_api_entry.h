@@ -2,8 +2,57 @@
 // srt_collider_surface, srt_texture_lookup, srt_material_normal, srt_primary_rays; the first-hit AOVs and
 // the denoiser (srt_render_aovs, srt_denoise; kernels in rt_denoise.h); device memory for the caller
 // (srt_device_alloc, srt_device_free, srt_memcpy); srt_mt19937_uniforms.
+// At its head, what only these entry points use: run_kernel, EventList, stage_in.
 // A fragment of rt_kernels.hip, included at its end and not compiled alone.  Before it: what stands above
-// its include in rt_kernels.hip; it uses (the API kernels, run_kernel, EventList, stage_in, finish_async, mt_launch).
+// its include in rt_kernels.hip; it uses (the API kernels, DevList, grid_for, check_flags, finish_async, mt_launch).
+namespace {
+
+// The shared tail of the single-kernel entry points: `kernel` over `n` items on the current slot's
+// stream, checked and waited for.  With `dflags` the kernel's flag word is read back and judged
+// (check_flags) into *flag_rc, which the entry point returns once its outputs are copied.
+template <typename K, typename... A>
+int run_kernel(srt_ctx* c, int64_t n, const uint32_t* dflags, int* flag_rc, K kernel, A... args) {
+    hipLaunchKernelGGL(kernel, dim3(grid_for(n, c->max_blocks)), dim3(BLOCK), 0, c->f->stream, args...);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->f->stream));
+    if (!dflags) return SRT_OK;
+    uint32_t flags = 0;
+    HIP_TRY(hipMemcpy(&flags, dflags, 4, hipMemcpyDefault));
+    *flag_rc = check_flags(flags);
+    return SRT_OK;
+}
+
+// HIP events of one call, destroyed with it
+struct EventList {
+    std::vector<hipEvent_t> e;
+    ~EventList() {
+        for (hipEvent_t v : e) (void)hipEventDestroy(v);
+    }
+    hipError_t create(int n) {
+        for (int i = 0; i < n; ++i) {
+            hipEvent_t v;
+            if (hipError_t rc = hipEventCreate(&v); rc != hipSuccess) return rc;
+            e.push_back(v);
+        }
+        return hipSuccess;
+    }
+};
+
+// an input array of a call: device memory is used in place, host memory is copied into a buffer of `bufs`
+template <typename T>
+hipError_t stage_in(DevList& bufs, const T* src, int64_t count, const T** dst) {
+    if (is_device_ptr(src)) {
+        *dst = src;
+        return hipSuccess;
+    }
+    T* p = nullptr;
+    const hipError_t e = bufs.in(&p, src, count);
+    *dst = p;
+    return e;
+}
+
+}  // namespace
+
 extern "C" {
 
 int srt_nearest(srt_ctx* c, const double* O, const double* D, int64_t n, double* t, int32_t* id, double* orient) {

@@ -340,7 +340,7 @@ constexpr int BVH_STACK = 32;  // (3 entries per 4-wide level at most: depth <= 
 constexpr int BVH_LDS = RT_BVH_LDS;  // (MAT_LDS_STACK) entries of a thread's stack kept in LDS, the rest private
 
 // The kernel's dynamic LDS: the texture tables [0, nlut_lds) staged by the trace kernels first
-// (rt_kernels.hip stage_luts), read directly (no pointer in the scene view, so the kernels' scene view
+// (rt_trace_kernels.h stage_luts), read directly (no pointer in the scene view, so the kernels' scene view
 // needs no per-block copy of their arguments)
 #if defined(__HIPCC__)
 extern __shared__ double rt_lds_dyn[];

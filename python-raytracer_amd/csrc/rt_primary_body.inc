@@ -1,4 +1,4 @@
-// rt_primary_body.inc -- the body of k_primary and k_primary_lean (rt_kernels.hip), included in both
+// rt_primary_body.inc -- the body of k_primary and k_primary_lean (rt_trace_kernels.h), included in both
 // kernels' definitions so that each reads its arguments in place from the kernel argument segment
 // (a __device__ function taking them by reference made the fused kernels' loads of them vector loads:
 // 23 -> 27 spilled VGPRs).  In scope: MATS, OCC, FUSE, LEAN and the kernel argument P0.

@@ -3,7 +3,7 @@
 `sRGB_to_sRGB_linear` is used on the host to build the 256-entry per-texture lookup tables that
 the kernels index with the raw texel byte (so a device texel fetch reproduces
 `load_image_as_linear_sRGB` exactly).  The frame resolve (`sRGB_linear_to_sRGB` + clip + u8) of a
-render runs on the device (`k_resolve` in `csrc/rt_kernels.hip`); these host versions remain part
+render runs on the device (`k_resolve` in `csrc/rt_aux_kernels.h`); these host versions remain part
 of the public API.
 """
 import numpy as np

@@ -2,7 +2,7 @@
 
 The product path is torch-free: the library splits a frame into 8-row bands dealt round-robin over
 the ranks (SRT_RENDER_SHARDED, rt_device.h shard_of_row / shard_local_row) and gathers the tiles
-to rank 0 over RCCL (rt_kernels.hip gather_post / k_assemble).  On the CPU:
+to rank 0 over RCCL (rt_kernels.hip gather_post / rt_aux_kernels.h k_assemble).  On the CPU:
   * the kernels' shard map (compiled for the CPU) against the numpy restatement (sightpy._shard);
   * a world-size-2 `gloo` job replays the gather protocol -- each rank sends its unpadded tile,
     rank 0 receives into padded staging and assembles with the kernels' map -- and must rebuild
