@@ -63,17 +63,20 @@ struct MtArgs {
 
 // Launches per round (k_mt_y only when no earlier end block made the key's y).
 //  k_mt_y: one workgroup: y = the 34 x 624 raw words generated from the key window, to HBM.
-//  k_mt_jump: one workgroup per segment s >= 1 that has anything to store.  y (HBM -> LDS), then
-//    W'[m] = XOR_{i : p_i} y[i + m] -- wave v of 8 takes coefficient words [78 v, 78 v + 78) (held
-//    one per lane, read out by v_readlane), lane g the eleven outputs m = 11 g .. 11 g + 10 with y[32 w + 11 g .. + 42] in registers
-//    (single-word LDS reads: the odd lane stride is free of bank conflicts); each coefficient bit is
-//    one v_bitop3 acc ^= y & mask per output, branch-free; the waves' partial windows are XOR-reduced
-//    through LDS and written to the window table.
-//  k_mt_gen: MT_GEN_THREADS per segment.  A ring of three 624-word blocks in LDS; the next block is
+//  k_mt_jump: `parts` workgroups per segment s >= 1 that has anything to store, each 1/parts of the
+//    polynomial's coefficient words.  Its slice of y (HBM -> LDS), then W'[m] = XOR_{i : p_i} y[i + m]
+//    -- wave v of 8 takes its share of the part's coefficient words (held one per lane, read out by
+//    v_readlane), lane g the eleven outputs m = 11 g .. 11 g + 10 with y[32 w + 11 g .. + 42] in
+//    registers (single-word LDS reads: the odd lane stride is free of bank conflicts); the
+//    coefficient bits are taken in pairs, one wave-uniform branch per pair around one in-place XOR
+//    per output (mt_jump_pair); the waves' partial windows are XOR-reduced through LDS and
+//    XOR-accumulated into the window table with atomics.
+//  k_mt_gen: MT_GEN_THREADS per segment.  A ring of eight 624-word blocks in LDS; the next block is
 //    made in three dependent stages of 227 / 227 / 170 words (x_{k+624} = x_{k+397} ^ twist(x_k,
-//    x_{k+1}): stage two and three take their x_{k+397} from the thread's own earlier word) while the
-//    current block's 312 doubles are tempered and stored.  7.5 KB of LDS and five waves per segment:
-//    the trace kernels of the previous frame keep the rest of the CU.
+//    x_{k+1}): stage two and three take their x_{k+397} from the thread's own earlier word) while
+//    finished blocks' doubles are tempered and stored, four blocks' 1248 pairs as one range where
+//    whole blocks follow each other (see k_mt_gen).  19.5 KB of LDS and five waves per segment (four
+//    beside a lean trace kernel): the trace kernels of the previous frame keep the rest of the CU.
 // 8 waves.  A jump block alone takes 111 us (16 waves: 74 us), but it must find room next to the
 // trace kernels of the frames in flight: a 16-wave block needs more registers per SIMD than one
 // finished trace block frees and waited up to 2.5 ms for whole CUs to drain.  Same box, ex1 1080p
@@ -124,21 +127,81 @@ __device__ __forceinline__ void mt_barrier() {
     __builtin_amdgcn_s_barrier();
 }
 
+// One bit pair of a jump coefficient word (k_mt_jump): the lane's eleven accumulators
+// a[k] ^= (pat & 1 ? r[k] : 0) ^ (pat & 2 ? r[k + 1] : 0), r the pair's twelve window words, `pat`
+// wave-uniform.  The dispatch on pat is written out as scalar branches around in-place
+// v_xor / v_bitop3 (every accumulator tied to one register): as C++ branches, however they were
+// arranged (an if-else chain, a switch, separate if-then blocks), the compiler restructured them into
+// blocks whose merges hand the accumulators over in fresh registers -- 176 v_mov_b32 per coefficient
+// word, a quarter of the loop's VALU instructions, and more with tied operands inside its branches.
+#define MT_JX(k, x) "v_xor_b32 %" #k ", %" #k ", %" #x "\n"
+#define MT_JX3(k, x, y) "v_bitop3_b32 %" #k ", %" #k ", %" #x ", %" #y " bitop3:0x96\n"
+__device__ __forceinline__ void mt_jump_pair(uint32_t (&a)[11], const uint32_t* r, uint32_t pat) {
+    asm("s_cmp_lt_u32 %23, 2\n"
+        "s_cbranch_scc1 .Lmtj_01_%=\n"
+        "s_cmp_eq_u32 %23, 2\n"
+        "s_cbranch_scc1 .Lmtj_2_%=\n"
+        MT_JX3(0, 11, 12) MT_JX3(1, 12, 13) MT_JX3(2, 13, 14) MT_JX3(3, 14, 15) MT_JX3(4, 15, 16) MT_JX3(5, 16, 17)
+        MT_JX3(6, 17, 18) MT_JX3(7, 18, 19) MT_JX3(8, 19, 20) MT_JX3(9, 20, 21) MT_JX3(10, 21, 22)
+        "s_branch .Lmtj_end_%=\n"
+        ".Lmtj_2_%=:\n"
+        MT_JX(0, 12) MT_JX(1, 13) MT_JX(2, 14) MT_JX(3, 15) MT_JX(4, 16) MT_JX(5, 17)
+        MT_JX(6, 18) MT_JX(7, 19) MT_JX(8, 20) MT_JX(9, 21) MT_JX(10, 22)
+        "s_branch .Lmtj_end_%=\n"
+        ".Lmtj_01_%=:\n"
+        "s_cmp_eq_u32 %23, 0\n"
+        "s_cbranch_scc1 .Lmtj_end_%=\n"
+        MT_JX(0, 11) MT_JX(1, 12) MT_JX(2, 13) MT_JX(3, 14) MT_JX(4, 15) MT_JX(5, 16)
+        MT_JX(6, 17) MT_JX(7, 18) MT_JX(8, 19) MT_JX(9, 20) MT_JX(10, 21)
+        ".Lmtj_end_%=:\n"
+        // (early-clobber: a[0] is written before the later r[] are read, so no input may share a
+        // register with an accumulator)
+        : "+&v"(a[0]), "+&v"(a[1]), "+&v"(a[2]), "+&v"(a[3]), "+&v"(a[4]), "+&v"(a[5]), "+&v"(a[6]), "+&v"(a[7]),
+          "+&v"(a[8]), "+&v"(a[9]), "+&v"(a[10])
+        : "v"(r[0]), "v"(r[1]), "v"(r[2]), "v"(r[3]), "v"(r[4]), "v"(r[5]), "v"(r[6]), "v"(r[7]), "v"(r[8]),
+          "v"(r[9]), "v"(r[10]), "v"(r[11]), "s"(pat)
+        : "scc");
+}
+#undef MT_JX
+#undef MT_JX3
+
+// rtmt::next_word in five instructions: the bit select and y ^ (mask & MATRIX_A) as three-input bit
+// operations ((a & c) | (b & ~c) and a ^ (b & c))
+__device__ __forceinline__ uint32_t mt_next_word(uint32_t xk, uint32_t xk1, uint32_t xkm) {
+    const uint32_t y = __builtin_amdgcn_bitop3_b32(xk, xk1, rtmt::UPPER, 0xE4);
+    const uint32_t odd = 0u - (xk1 & 1u);
+    return xkm ^ __builtin_amdgcn_bitop3_b32(y >> 1, odd, rtmt::MATRIX_A, 0x78);
+}
+
 // block n (624 words) from block p by a workgroup.  Thread t < 227 makes words t, 227 + t and 454 + t:
 // each needs only block p and the thread's own earlier word, so no barrier is needed inside the
-// block; word 623 also needs word 0 of block n, which thread 169 recomputes.
-__device__ __forceinline__ void mt_next_block(const uint32_t* p, uint32_t* n, int t) {
+// block; word 623 also needs word 0 of block n, which thread 169 recomputes.  `last_copy` (uniform,
+// may be null): where word 623 is stored a second time (k_mt_gen's ring).
+__device__ __forceinline__ void mt_next_block(const uint32_t* p, uint32_t* n, int t, uint32_t* last_copy = nullptr) {
     if (t < 227) {
         const uint32_t a0 = p[t], a1 = p[t + 1], a2 = p[t + 397], b0 = p[227 + t], b1 = p[228 + t];
         const uint32_t c0 = t < 170 ? p[454 + t] : 0u;
         uint32_t c1 = t < 169 ? p[455 + t] : 0u;
-        const uint32_t wa = rtmt::next_word(a0, a1, a2);
-        const uint32_t wb = rtmt::next_word(b0, b1, wa);
+        const uint32_t wa = mt_next_word(a0, a1, a2);
+        const uint32_t wb = mt_next_word(b0, b1, wa);
         n[t] = wa;
         n[227 + t] = wb;
-        if (t == 169) c1 = rtmt::next_word(p[0], p[1], p[397]);  // word 0 of block n
-        if (t < 170) n[454 + t] = rtmt::next_word(c0, c1, wb);
+        if (t == 169) c1 = mt_next_word(p[0], p[1], p[397]);  // word 0 of block n
+        if (t < 170) {
+            const uint32_t wc = mt_next_word(c0, c1, wb);
+            n[454 + t] = wc;
+            if (last_copy && t == 169) *last_copy = wc;
+        }
     }
+}
+
+// rtmt::temper, each y ^= (y << s) & C as one shift and one three-input bit operation a ^ (b & c)
+__device__ __forceinline__ uint32_t mt_temper(uint32_t y) {
+    y ^= y >> 11;
+    y = __builtin_amdgcn_bitop3_b32(y, y << 7, 0x9D2C5680u, 0x78);
+    y = __builtin_amdgcn_bitop3_b32(y, y << 15, 0xEFC60000u, 0x78);
+    y ^= y >> 18;
+    return y;
 }
 
 // What segment s of a round stores and generates (uniform over the segment's threads).
@@ -283,20 +346,9 @@ __global__ __launch_bounds__(MT_THREADS) void k_mt_jump(MtArgs A, uint32_t* win)
         // mt_jump_bench.cpp, 204 bands): pairs with a pre-XORed pair row 74 us; a v_bitop3 acc ^= y &
         // mask per bit, branch-free, 117 us; a uniform branch per bit 108 us; nibbles (xor3 of two pair
         // rows) 172 us
+        static_assert(MT_G == 11, "mt_jump_pair is written for eleven accumulators");
 #pragma unroll
-        for (int j = 0; j < 32; j += 2) {
-            const uint32_t pat = (cw >> j) & 3u;  // wave-uniform
-            if (pat == 1u) {
-#pragma unroll
-                for (int k = 0; k < MT_G; ++k) acc[k] ^= r[j + k];
-            } else if (pat == 2u) {
-#pragma unroll
-                for (int k = 0; k < MT_G; ++k) acc[k] ^= r[j + 1 + k];
-            } else if (pat == 3u) {
-#pragma unroll
-                for (int k = 0; k < MT_G; ++k) acc[k] = __builtin_amdgcn_bitop3_b32(acc[k], r[j + k], r[j + 1 + k], 0x96);
-            }
-        }
+        for (int j = 0; j < 32; j += 2) mt_jump_pair(acc, r + j, (cw >> j) & 3u);
     }
     __syncthreads();  // every wave is done reading y
 #pragma unroll
@@ -342,9 +394,32 @@ __global__ __launch_bounds__(MT_THREADS) void k_mt_jump(MtArgs A, uint32_t* win)
 // workgroup form (threads < 227 make three words each).  The window, once read, is zeroed for the
 // next generation's jump parts to XOR into (no memset launch on the generation's critical path:
 // behind the trace kernels of the frames in flight a 150 KB fill waited 36-133 us for a CU).
+//
+// The workgroup form has two paths.  Runs of whole blocks -- all 312 pairs stored, one stored plane,
+// no band mask, no chain or dump window -- go MT_SUPER blocks at a time: their 1248 pairs are one
+// linear range of the ring, taken in ceil(1248 / NT) store passes (five of 256 lanes, the last with
+// 224, where a block at a time took two passes with 56 lanes in the second), each pass in the step
+// that completes its last word; the run's length is computed once, and the passes test nothing but
+// the last one's lane bound.  A segment's first and last blocks, plane crossings, masked bands and
+// the chain and dump blocks take the general path, a block at a time.  The ring holds MT_RING blocks
+// (19.5 KB; three blocks, 7.5 KB, in the one-wave form): a super-iteration starts at slot 0 or 4, so
+// its blocks and the block before them (the first word of a pair that straddles two blocks) are
+// contiguous, slot 7's last word being kept a second time in front of slot 0.
+constexpr int MT_RING = 8, MT_SUPER = 4;
+constexpr int MT_SUPER_PAIRS = MT_SUPER * rtmt::N / 2;
+
+// whole blocks from word b0 on that end at or before the 624-word window at `at` (every block when
+// b0 lies behind the window)
+__device__ __forceinline__ int64_t mt_blocks_before(int64_t b0, int64_t at) {
+    return b0 >= at + rtmt::N ? INT64_MAX : at >= b0 ? (at - b0) / rtmt::N : 0;
+}
+
 template <int NT>
 __global__ __launch_bounds__(NT) void k_mt_gen(MtArgs A, uint32_t* win) {
-    __shared__ uint32_t ring[3 * rtmt::N];
+    constexpr bool WG = NT >= 256;
+    constexpr int R = WG ? MT_RING : 3;
+    __shared__ uint32_t ring_mem[2 + R * rtmt::N];
+    uint32_t* const ring = ring_mem + 2;  // ring[-1]: the copy of slot R - 1's last word
     if (MT_WAVE_PRIO) __builtin_amdgcn_s_setprio(MT_WAVE_PRIO);  // (ahead of the trace waves)
     const int s = blockIdx.x;
     const int lane = threadIdx.x;
@@ -356,9 +431,12 @@ __global__ __launch_bounds__(NT) void k_mt_gen(MtArgs A, uint32_t* win) {
             for (int m = lane; m < rtmt::N; m += NT) w0p[m] = 0u;
         return;
     }
+    // block 0 (the window) goes to slot 3: block 1, the first whole one of most segments, is then at
+    // slot 4, where a super-iteration may start
+    constexpr int SLOT0 = WG ? MT_SUPER - 1 : 0;
     const uint32_t* src = w0p ? w0p : A.key;
     for (int m = lane; m < rtmt::N; m += NT) {
-        ring[m] = src[m];
+        ring[SLOT0 * rtmt::N + m] = src[m];
         if (w0p) w0p[m] = 0u;  // (each thread zeroes the words it read)
     }
     __syncthreads();
@@ -374,12 +452,60 @@ __global__ __launch_bounds__(NT) void k_mt_gen(MtArgs A, uint32_t* win) {
         kb = (pidx + 1) * A.plane - g.dbase;
     }
     int kq = c0;  // pair of block q's first thread slot
-    int slot = 0, prev = 2, next = 1;
+    int slot = SLOT0, prev = SLOT0 == 0 ? R - 1 : SLOT0 - 1, next = SLOT0 + 1;
     for (int64_t b0 = g.ws; b0 < g.gen_end; b0 += rtmt::N) {
+        if (kq >= kb) {
+            ++pidx;
+            kb += A.plane;
+        }
+        if constexpr (WG) {
+            // whole blocks from this one on, counted once per run; a run goes MT_SUPER blocks at a time
+            int64_t nblk = 0;
+            if ((slot & (MT_SUPER - 1)) == 0 && !g.masked && kq >= 0) {
+                int64_t kstop = g.kend;  // the run's pairs end here: the segment's, or the plane's
+                if (A.plane > 0) kstop = ((A.plane_mask >> (int)(pidx & 3)) & 1) ? min(kstop, kb) : 0;
+                nblk = (kstop - kq) / (rtmt::N / 2);
+                if (g.chain) nblk = min(nblk, mt_blocks_before(b0, g.chain_at));
+                if (g.dump) nblk = min(nblk, mt_blocks_before(b0, A.dump_at));
+            }
+            if (nblk >= MT_SUPER) {
+                constexpr int NP = (MT_SUPER_PAIRS + NT - 1) / NT;  // store passes per super-iteration
+                const int nsup = (int)(nblk / MT_SUPER);
+                // pair slot t of the run's current MT_SUPER blocks: words xb[2 t], xb[2 t + 1] (a segment of
+                // odd offset takes the first from the word before), stored at po[t]
+                const int odd = off0 & 1;
+                double* po = outp + kq + lane;
+                for (int it = 0; it < nsup; ++it) {
+                    const uint32_t* base = ring + slot * rtmt::N;
+                    const uint32_t* xb = base - odd + 2 * lane;
+#pragma unroll
+                    for (int i = 0; i < MT_SUPER; ++i) {
+                        const int sn = slot + i + 1;  // 1 .. R
+                        mt_next_block(base + i * rtmt::N, ring + (sn & (R - 1)) * rtmt::N, lane,
+                                      sn == R - 1 ? ring - 1 : nullptr);
+#pragma unroll
+                        for (int ps = 0; ps < NP; ++ps) {
+                            // pass ps needs words up to 2 NT (ps + 1) - 1: complete in step i = that / 624
+                            if (min(MT_SUPER - 1, (2 * NT * (ps + 1) - 1) / rtmt::N) != i) continue;
+                            if (NT * (ps + 1) <= MT_SUPER_PAIRS || NT * ps + lane < MT_SUPER_PAIRS)
+                                po[NT * ps] = rtmt::to_double(mt_temper(xb[2 * NT * ps]), mt_temper(xb[2 * NT * ps + 1]));
+                        }
+                        mt_barrier();
+                    }
+                    po += MT_SUPER_PAIRS;
+                    slot = (slot + MT_SUPER) & (R - 1);
+                }
+                kq += nsup * MT_SUPER_PAIRS;
+                b0 += (int64_t)(nsup * MT_SUPER - 1) * rtmt::N;  // (the loop adds the last block)
+                prev = (slot + R - 1) & (R - 1);
+                next = slot + 1;
+                continue;
+            }
+        }
         const uint32_t* p = ring + slot * rtmt::N;
         uint32_t* n = ring + next * rtmt::N;
-        if (NT >= 256) {
-            if (b0 + rtmt::N < g.gen_end) mt_next_block(p, n, lane);
+        if (WG) {
+            if (b0 + rtmt::N < g.gen_end) mt_next_block(p, n, lane, next == R - 1 ? ring - 1 : nullptr);
         } else if (b0 + rtmt::N < g.gen_end) {
             // stage 1: words j < 227; stage 2: 227 + j; stage 3: 454 + j (j < 170), chunk c = lane + 64 c
             uint32_t wa[4], wb[4];
@@ -401,10 +527,6 @@ __global__ __launch_bounds__(NT) void k_mt_gen(MtArgs A, uint32_t* win) {
                 if (j < 170) n[454 + j] = rtmt::next_word(p[454 + j], j == 169 ? n0 : p[min(455 + j, 623)], wb[c]);
             }
         }
-        if (kq >= kb) {
-            ++pidx;
-            kb += A.plane;
-        }
         const uint32_t* cur = p;
         // the block's pairs k in [klo, khi) are all stored when no merged-band mask applies and the
         // (at most two) planes they lie in are stored planes: one range test per pair (the usual
@@ -423,7 +545,7 @@ __global__ __launch_bounds__(NT) void k_mt_gen(MtArgs A, uint32_t* win) {
                     const int o = off0 + 2 * (c0 + t);  // in-block offset of the pair's first word: -1 .. 622
                     const uint32_t x0 = o >= 0 ? cur[o] : ring[prev * rtmt::N + rtmt::N - 1];
                     const uint32_t x1 = cur[o + 1];
-                    outp[k] = rtmt::to_double(rtmt::temper(x0), rtmt::temper(x1));
+                    outp[k] = rtmt::to_double(mt_temper(x0), mt_temper(x1));
                 }
             }
         } else {
@@ -440,7 +562,7 @@ __global__ __launch_bounds__(NT) void k_mt_gen(MtArgs A, uint32_t* win) {
                     const int64_t ko = cm ? (int64_t)((uint32_t)k / (uint32_t)A.band_period) * A.band_len +
                                                 (uint32_t)k % (uint32_t)A.band_period
                                           : (int64_t)k;
-                    outp[ko] = rtmt::to_double(rtmt::temper(x0), rtmt::temper(x1));
+                    outp[ko] = rtmt::to_double(mt_temper(x0), mt_temper(x1));
                 }
             }
         }
@@ -455,7 +577,7 @@ __global__ __launch_bounds__(NT) void k_mt_gen(MtArgs A, uint32_t* win) {
         kq += 312;
         prev = slot;
         slot = next;
-        next = next == 2 ? 0 : next + 1;
+        next = next == R - 1 ? 0 : next + 1;
         // (one wave: its LDS operations complete in order, the barrier is nearly free; the output
         // stores are not waited for)
         mt_barrier();

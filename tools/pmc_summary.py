@@ -26,6 +26,11 @@ launch (MI355X_MICROARCH.md § HBM and § Execution model):
     python tools/pmc_summary.py gpurun_out/pmc_a gpurun_out/pmc_b ... --out profiles/r03_counters_X.json
     python tools/pmc_summary.py --recompute profiles/r02_counters_X.json ...   (derived fields again
                                                                                  from stored counters)
+
+--per-dispatch adds "per_dispatch": every launch of the kernels whose name holds one of --kernels
+(comma-separated substrings; default all), with its grid and workgroup size and its counters, in
+dispatch order.  The per-launch means above mix launches of different shapes (a pipeline's first frame
+generates its stream in other segments than the steady ones); the list keeps them apart.
 """
 import argparse
 import csv
@@ -54,6 +59,21 @@ def load(dirpath):
             for c, v in cs.items():
                 per[short(k)][c].append(v)
     return per
+
+
+def load_dispatches(dirpath, names):
+    """[{dispatch, kernel, grid, workgroup, <counter>: value, ...}] in dispatch order."""
+    rows = {}
+    for f in glob.glob(os.path.join(dirpath, "**", "*counter_collection.csv"), recursive=True):
+        for r in csv.DictReader(open(f)):
+            k = short(r["Kernel_Name"]).replace("void ", "")
+            if names and not any(n in k for n in names):
+                continue
+            d = rows.setdefault(int(r["Dispatch_Id"]), {"dispatch": int(r["Dispatch_Id"]), "kernel": k,
+                                                          "grid": int(r["Grid_Size"]),
+                                                          "workgroup": int(r["Workgroup_Size"])})
+            d[r["Counter_Name"]] = float(r["Counter_Value"])
+    return [rows[i] for i in sorted(rows)]
 
 
 DERIVED = {"traffic_bytes": "2 x FETCH_SIZE x 1024 + WRITE_SIZE x 1024",
@@ -109,6 +129,8 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--label", default="")
     ap.add_argument("--recompute", nargs="+", help="summary files whose derived fields are recomputed")
+    ap.add_argument("--per-dispatch", action="store_true", help="also list every launch with its counters")
+    ap.add_argument("--kernels", default="", help="with --per-dispatch: comma-separated kernel name substrings")
     a = ap.parse_args()
     if a.recompute:
         return recompute(a.recompute)
@@ -126,6 +148,9 @@ def main():
         rec = {"counters": c, "launches": launches[k]}
         rec.update(derive(c))
         out["kernels"][k] = rec
+    if a.per_dispatch:
+        names = [n for n in a.kernels.split(",") if n]
+        out["per_dispatch"] = [d for p in a.dirs for d in load_dispatches(p, names)]
     with open(a.out, "w") as fh:
         json.dump(out, fh, indent=1)
     for k, r in out["kernels"].items():
