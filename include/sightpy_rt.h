@@ -29,8 +29,9 @@
  *   srt_texture_lookup     <- image.get_color(hit)     sightpy/textures/texture.py:32-39
  *   srt_material_normal    <- Material.get_Normal(hit) sightpy/materials/material.py:18-36
  *   srt_primary_rays       <- Camera.get_ray(n)       sightpy/camera.py:51-85
- *   srt_render_aovs, srt_denoise: no counterpart (first-hit guide images and the a-trous filter that
- *                             denoises a low-sample frame with them)
+ *   srt_render_aovs, srt_denoise, srt_denoise_var: no counterpart (first-hit guide images and the a-trous
+ *                             filter that denoises a low-sample frame with them; _var: from two half-frames,
+ *                             with their difference as the per-pixel noise estimate)
  *   srt_upload_scene       <- (scene lowering; the reference deep-copies the Scene per task,
  *                              scene.py:85)
  *
@@ -498,6 +499,53 @@ typedef struct srt_denoise_args {
                                from the first launch to the end of the resolve (HIP events), or NULL */
 } srt_denoise_args;
 int srt_denoise(srt_ctx* ctx, int32_t width, int32_t height, const srt_denoise_args* args);
+
+/* srt_denoise_var: the same filter over a frame given as two half-frames, with a per-pixel noise estimate
+ * from their difference (SRT_DENOISE_VARIANCE) and / or albedo demodulation (SRT_DENOISE_DEMODULATE); the
+ * two flags are independent, and with neither the result is srt_denoise's of c, bit for bit.  All float64,
+ * in the order written.  A = rgb_a (mean of ka = spp_a samples), B = rgb_b (mean of kb = spp_b samples),
+ * spp = ka + kb, lum(x) = (0.2126 x.r + 0.7152 x.g) + 0.0722 x.b.
+ *   prepare:  c = (ka * A + kb * B) / spp;  ok = p is not background and A, B are finite
+ *             DEMODULATE and ok: d = max(albedo, 1e-3) per channel, uA = A / d, uB = B / d, u = c / d
+ *             otherwise:         uA = A, uB = B, u = c
+ *             v = ((ka * kb) / (spp * spp)) * (lum(uA) - lum(uB))^2 when ok, else 0
+ *   level l:  srt_denoise's level on u.  With VARIANCE its colour term is
+ *               |lum(u_p) - lum(u_q)| / (sigma_lum * sqrt(g_p) + 1e-8)      (no halving per level)
+ *             level 0: g_p = sum(k * v_q) / sum(k), k = (1/4, 1/2, 1/4) x (1/4, 1/2, 1/4) over q = p + (dx, dy),
+ *             dy = -1..1 (outer), dx = -1..1 (inner), q inside the image and not background; levels l >= 1:
+ *             g_p = v_p of the level's own v (so that a noise-free region stays untouched at every level);
+ *             u'_p = sum(w * u_q) / sum(w), v'_p = sum(w^2 * v_q) / sum(w)^2; a pixel copied through keeps v
+ *   finish:   DEMODULATE: c' = u' * d where prepare divided; elsewhere, and without it, c' = u' (on
+ *             background and non-finite pixels that is c itself)
+ * Pointers may address host or device memory (device arrays are used in place).  Needs no scene.
+ * SRT_ERR_ARG: spp_a or spp_b <= 0, a sigma in use <= 0 (sigma_color without VARIANCE, sigma_lum with it,
+ * the other three always), levels outside 0..8, a NULL input, a non-positive size, no output (out_rgb
+ * and out_srgb8 both NULL), out_variance without VARIANCE, an unknown flag. */
+#define SRT_DENOISE_VARIANCE 4   /* the colour weight from the half-frames' difference (sigma_lum) */
+#define SRT_DENOISE_DEMODULATE 8 /* filter c / max(albedo, 1e-3), multiply back afterwards */
+typedef struct srt_denoise_var_args {
+    const double* rgb_a;    /* [3][n] linear RGB, mean of spp_a samples */
+    const double* rgb_b;    /* [3][n] linear RGB, mean of spp_b samples */
+    int32_t spp_a;
+    int32_t spp_b;
+    const double* normal;   /* [3][n] */
+    const double* albedo;   /* [3][n] */
+    const double* position; /* [3][n] */
+    const double* depth;    /* [n] */
+    int32_t levels;         /* 0..8 */
+    int32_t flags;          /* SRT_DENOISE_RGBX | SRT_DENOISE_VARIANCE | SRT_DENOISE_DEMODULATE */
+    double sigma_color;     /* used without SRT_DENOISE_VARIANCE */
+    double sigma_lum;       /* used with SRT_DENOISE_VARIANCE */
+    double sigma_normal;
+    double sigma_albedo;
+    double sigma_plane;
+    double* out_rgb;        /* [3][n] filtered linear RGB c', or NULL */
+    double* out_variance;   /* [n] the last level's v (prepare's with levels = 0), or NULL; needs VARIANCE */
+    uint8_t* out_srgb8;     /* [n][3] ([n][4] with SRT_DENOISE_RGBX), or NULL */
+    double* ms_levels;      /* host [levels + 2]: each level's kernel, the whole chain (prepare to the end of the
+                               resolve), then the prepare kernel alone (HIP events), or NULL */
+} srt_denoise_var_args;
+int srt_denoise_var(srt_ctx* ctx, int32_t width, int32_t height, const srt_denoise_var_args* args);
 /* numpy's legacy global-RNG stream on the device: writes the n_out doubles that
  * `np.random.rand(n_out)` would return for the RandomState with MT19937 key[624] and position
  * pos (0..624, as in np.random.get_state()), then consumes n_skip more draws, and returns the

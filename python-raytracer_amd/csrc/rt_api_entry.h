@@ -1,6 +1,6 @@
 // rt_api_entry.h -- entry points of one kernel each: srt_nearest, srt_intersect_collider,
 // srt_collider_surface, srt_texture_lookup, srt_material_normal, srt_primary_rays; the first-hit AOVs and
-// the denoiser (srt_render_aovs, srt_denoise; kernels in rt_denoise.h); device memory for the caller
+// the denoiser (srt_render_aovs, srt_denoise, srt_denoise_var; kernels in rt_denoise.h); device memory for the caller
 // (srt_device_alloc, srt_device_free, srt_memcpy); srt_mt19937_uniforms.
 // At its head, what only these entry points use: run_kernel, EventList, stage_in.
 // A fragment of rt_kernels.hip, included at its end and not compiled alone.  Before it: what stands above
@@ -306,7 +306,7 @@ int srt_denoise(srt_ctx* c, int32_t width, int32_t height, const srt_denoise_arg
         K.sn2 = a->sigma_normal * a->sigma_normal;
         K.sa2 = a->sigma_albedo * a->sigma_albedo;
         K.sp2 = a->sigma_plane * a->sigma_plane;
-        hipLaunchKernelGGL(k_atrous, dim3(grid), dim3(DN_BLOCK), 0, st, G, K, pong[l & 1]);
+        hipLaunchKernelGGL(k_atrous<false>, dim3(grid), dim3(DN_BLOCK), 0, st, G, K, pong[l & 1], AtrousVar{});
         HIP_TRY(hipGetLastError());
         if (a->ms_levels) HIP_TRY(hipEventRecord(ev.e[(size_t)l + 1], st));
         G.rgb = pong[l & 1];
@@ -325,6 +325,108 @@ int srt_denoise(srt_ctx* c, int32_t width, int32_t height, const srt_denoise_arg
         a->ms_levels[l] = ms;
     }
     if (a->out_rgb && a->out_rgb != G.rgb) HIP_TRY(bufs.copy(a->out_rgb, G.rgb, 3 * n));
+    if (a->out_srgb8 && du8 != a->out_srgb8) HIP_TRY(bufs.copy(a->out_srgb8, (const uint8_t*)du8, u8_bytes));
+    return SRT_OK;
+}
+
+int srt_denoise_var(srt_ctx* c, int32_t width, int32_t height, const srt_denoise_var_args* a) {
+    if (!c || !a) return fail(SRT_ERR_ARG, "null argument");
+    if (width <= 0 || height <= 0) return fail(SRT_ERR_ARG, "srt_denoise_var: non-positive image size");
+    if (!a->rgb_a || !a->rgb_b || !a->normal || !a->albedo || !a->position || !a->depth)
+        return fail(SRT_ERR_ARG, "srt_denoise_var: NULL half-frame or guide array");
+    if (a->spp_a <= 0 || a->spp_b <= 0) return fail(SRT_ERR_ARG, "srt_denoise_var: spp_a and spp_b must be positive");
+    if (a->levels < 0 || a->levels > SRT_DENOISE_MAX_LEVELS) return fail(SRT_ERR_ARG, "srt_denoise_var: levels outside 0..8");
+    if (a->flags & ~(SRT_DENOISE_RGBX | SRT_DENOISE_VARIANCE | SRT_DENOISE_DEMODULATE))
+        return fail(SRT_ERR_ARG, "srt_denoise_var: unknown flag");
+    const bool var = (a->flags & SRT_DENOISE_VARIANCE) != 0, demod = (a->flags & SRT_DENOISE_DEMODULATE) != 0;
+    if (!((var ? a->sigma_lum : a->sigma_color) > 0.0) || !(a->sigma_normal > 0.0) || !(a->sigma_albedo > 0.0) ||
+        !(a->sigma_plane > 0.0))
+        return fail(SRT_ERR_ARG, "srt_denoise_var: the sigmas in use must be positive");
+    if (!a->out_rgb && !a->out_srgb8) return fail(SRT_ERR_ARG, "srt_denoise_var: no output");
+    if (a->out_variance && !var) return fail(SRT_ERR_ARG, "srt_denoise_var: out_variance needs SRT_DENOISE_VARIANCE");
+    HIP_TRY(hipSetDevice(c->device));
+    DevList bufs;
+    const int64_t n = (int64_t)width * height;
+    DnHalves F{};
+    F.ka = a->spp_a, F.kb = a->spp_b, F.spp = (double)a->spp_a + (double)a->spp_b;
+    F.demod = demod ? 1 : 0;
+    AtrousPlanes G{};
+    G.npix = n;
+    G.W = width;
+    HIP_TRY(stage_in(bufs, a->rgb_a, 3 * n, &F.a));
+    HIP_TRY(stage_in(bufs, a->rgb_b, 3 * n, &F.b));
+    HIP_TRY(stage_in(bufs, a->normal, 3 * n, &G.normal));
+    HIP_TRY(stage_in(bufs, a->albedo, 3 * n, &G.albedo));
+    HIP_TRY(stage_in(bufs, a->position, 3 * n, &G.position));
+    HIP_TRY(stage_in(bufs, a->depth, n, &G.depth));
+    // prepare writes cb[0] / vb[0]; level l reads buffer l & 1 and writes the other one
+    double *cb[2] = {nullptr, nullptr}, *vb[2] = {nullptr, nullptr};
+    for (int k = 0; k < std::min(a->levels + 1, 2); ++k) {
+        HIP_TRY(bufs.alloc(&cb[k], 3 * n));
+        if (var) HIP_TRY(bufs.alloc(&vb[k], n));
+    }
+    const bool rgbx = (a->flags & SRT_DENOISE_RGBX) != 0;
+    const int64_t u8_bytes = n * (rgbx ? 4 : 3);
+    uint8_t* du8 = nullptr;
+    if (a->out_srgb8) {
+        if (is_device_ptr(a->out_srgb8))
+            du8 = a->out_srgb8;
+        else
+            HIP_TRY(bufs.alloc(&du8, u8_bytes));
+    }
+    EventList ev;
+    if (a->ms_levels) HIP_TRY(ev.create(a->levels + 3));  // before and after prepare, after each level, the end
+    hipStream_t st = c->f->stream;
+    const int64_t segs = ((int64_t)width + 63) / 64;
+    const int grid = grid_for(segs * height * 64, c->max_blocks), grid_px = grid_for(n, c->max_blocks);
+    if (a->ms_levels) HIP_TRY(hipEventRecord(ev.e[0], st));
+    hipLaunchKernelGGL(k_dn_prepare, dim3(grid_px), dim3(DN_BLOCK), 0, st, F, G.normal, G.albedo, n, cb[0], vb[0]);
+    HIP_TRY(hipGetLastError());
+    if (a->ms_levels) HIP_TRY(hipEventRecord(ev.e[1], st));
+    G.rgb = cb[0];
+    for (int l = 0; l < a->levels; ++l) {
+        AtrousLevel K{};
+        K.W = width, K.H = height, K.step = 1 << l;
+        const double sc = a->sigma_color * ldexp(1.0, -l);
+        K.sc2 = sc * sc;
+        K.sn2 = a->sigma_normal * a->sigma_normal;
+        K.sa2 = a->sigma_albedo * a->sigma_albedo;
+        K.sp2 = a->sigma_plane * a->sigma_plane;
+        double* out = cb[(l + 1) & 1];
+        if (var)
+            hipLaunchKernelGGL(k_atrous<true>, dim3(grid), dim3(DN_BLOCK), 0, st, G, K, out,
+                               AtrousVar{vb[l & 1], vb[(l + 1) & 1], a->sigma_lum});
+        else
+            hipLaunchKernelGGL(k_atrous<false>, dim3(grid), dim3(DN_BLOCK), 0, st, G, K, out, AtrousVar{});
+        HIP_TRY(hipGetLastError());
+        if (a->ms_levels) HIP_TRY(hipEventRecord(ev.e[(size_t)l + 2], st));
+        G.rgb = out;
+    }
+    double* res = cb[a->levels & 1];  // == G.rgb
+    if (demod) {
+        hipLaunchKernelGGL(k_dn_finish, dim3(grid_px), dim3(DN_BLOCK), 0, st, F, G.normal, G.albedo, n, res, du8,
+                           rgbx ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+    } else if (du8) {
+        hipLaunchKernelGGL(k_denoise_resolve, dim3(grid_px), dim3(DN_BLOCK), 0, st, (const double*)res, n, du8,
+                           rgbx ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+    }
+    if (a->ms_levels) HIP_TRY(hipEventRecord(ev.e[(size_t)a->levels + 2], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (a->ms_levels) {
+        float ms = 0.f;
+        for (int l = 0; l < a->levels; ++l) {
+            HIP_TRY(hipEventElapsedTime(&ms, ev.e[(size_t)l + 1], ev.e[(size_t)l + 2]));
+            a->ms_levels[l] = ms;
+        }
+        HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[(size_t)a->levels + 2]));
+        a->ms_levels[a->levels] = ms;
+        HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+        a->ms_levels[a->levels + 1] = ms;
+    }
+    if (a->out_rgb) HIP_TRY(bufs.copy(a->out_rgb, (const double*)res, 3 * n));
+    if (a->out_variance) HIP_TRY(bufs.copy(a->out_variance, (const double*)vb[a->levels & 1], n));
     if (a->out_srgb8 && du8 != a->out_srgb8) HIP_TRY(bufs.copy(a->out_srgb8, (const uint8_t*)du8, u8_bytes));
     return SRT_OK;
 }

@@ -380,7 +380,8 @@ int hc_denoise(int32_t width, int32_t height, const srt_denoise_args* a) {
         o.resize((size_t)(3 * n));
         for (int32_t y = 0; y < height; ++y)
             for (int32_t x = 0; x < width; ++x) {
-                const d3 c = atrous_pixel(G, K, x, y);
+                double v;
+                const d3 c = atrous_pixel<false>(G, K, AtrousVar{}, x, y, v);
                 const int64_t ip = (int64_t)y * width + x;
                 o[(size_t)ip] = c.x; o[(size_t)(n + ip)] = c.y; o[(size_t)(2 * n + ip)] = c.z;
             }
@@ -395,6 +396,71 @@ int hc_denoise(int32_t width, int32_t height, const srt_denoise_args* a) {
             if (rgbx) px[3] = 255;
         }
     if (a->out_rgb) std::memmove(a->out_rgb, G.rgb, (size_t)(3 * n) * sizeof(double));
+    return SRT_OK;
+}
+
+// srt_denoise_var: k_dn_prepare, the levels of k_atrous<VAR> over two colour (and variance) buffers,
+// k_dn_finish / k_denoise_resolve
+int hc_denoise_var(int32_t width, int32_t height, const srt_denoise_var_args* a) {
+    const bool var = (a->flags & SRT_DENOISE_VARIANCE) != 0, demod = (a->flags & SRT_DENOISE_DEMODULATE) != 0;
+    if (width <= 0 || height <= 0 || !a->rgb_a || !a->rgb_b || !a->normal || !a->albedo || !a->position || !a->depth ||
+        a->spp_a <= 0 || a->spp_b <= 0 || a->levels < 0 || a->levels > SRT_DENOISE_MAX_LEVELS ||
+        (a->flags & ~(SRT_DENOISE_RGBX | SRT_DENOISE_VARIANCE | SRT_DENOISE_DEMODULATE)) ||
+        !((var ? a->sigma_lum : a->sigma_color) > 0.0) || !(a->sigma_normal > 0.0) || !(a->sigma_albedo > 0.0) ||
+        !(a->sigma_plane > 0.0) || (!a->out_rgb && !a->out_srgb8) || (a->out_variance && !var)) {
+        g_err = "hc_denoise_var: bad argument";
+        return SRT_ERR_ARG;
+    }
+    const int64_t n = (int64_t)width * height;
+    DnHalves F{a->rgb_a, a->rgb_b, (double)a->spp_a, (double)a->spp_b, (double)a->spp_a + (double)a->spp_b, demod ? 1 : 0};
+    const auto at = [n](const double* p, int64_t i) { return d3{p[i], p[n + i], p[2 * n + i]}; };
+    std::vector<double> cb[2], vb[2];
+    for (int k = 0; k < 2; ++k) {
+        cb[k].resize((size_t)(3 * n));
+        vb[k].resize((size_t)n);
+    }
+    for (int64_t i = 0; i < n; ++i) {
+        const DnPrepared r = dn_prepare_pixel(F, at(F.a, i), at(F.b, i), at(a->normal, i), at(a->albedo, i));
+        cb[0][(size_t)i] = r.u.x; cb[0][(size_t)(n + i)] = r.u.y; cb[0][(size_t)(2 * n + i)] = r.u.z;
+        vb[0][(size_t)i] = r.v;
+    }
+    AtrousPlanes G{cb[0].data(), a->normal, a->albedo, a->position, a->depth, n, width};
+    for (int l = 0; l < a->levels; ++l) {
+        AtrousLevel K{};
+        K.W = width, K.H = height, K.step = 1 << l;
+        const double sc = a->sigma_color * ldexp(1.0, -l);
+        K.sc2 = sc * sc;
+        K.sn2 = a->sigma_normal * a->sigma_normal;
+        K.sa2 = a->sigma_albedo * a->sigma_albedo;
+        K.sp2 = a->sigma_plane * a->sigma_plane;
+        std::vector<double>& o = cb[(l + 1) & 1];
+        const AtrousVar V{vb[l & 1].data(), vb[(l + 1) & 1].data(), a->sigma_lum};
+        for (int32_t y = 0; y < height; ++y)
+            for (int32_t x = 0; x < width; ++x) {
+                double v = 0.0;
+                const d3 c = var ? atrous_pixel<true>(G, K, V, x, y, v) : atrous_pixel<false>(G, K, V, x, y, v);
+                const int64_t ip = (int64_t)y * width + x;
+                o[(size_t)ip] = c.x; o[(size_t)(n + ip)] = c.y; o[(size_t)(2 * n + ip)] = c.z;
+                V.v_out[ip] = v;
+            }
+        G.rgb = o.data();
+    }
+    double* res = cb[a->levels & 1].data();
+    if (demod)
+        for (int64_t i = 0; i < n; ++i) {
+            const d3 c = dn_finish_pixel(at(res, i), at(F.a, i), at(F.b, i), at(a->normal, i), at(a->albedo, i));
+            res[i] = c.x; res[n + i] = c.y; res[2 * n + i] = c.z;
+        }
+    const bool rgbx = (a->flags & SRT_DENOISE_RGBX) != 0;
+    if (a->out_srgb8)
+        for (int64_t i = 0; i < n; ++i) {
+            const uint32_t v = denoise_resolve(at(res, i));
+            uint8_t* px = a->out_srgb8 + (rgbx ? 4 : 3) * i;
+            px[0] = (uint8_t)v; px[1] = (uint8_t)(v >> 8); px[2] = (uint8_t)(v >> 16);
+            if (rgbx) px[3] = 255;
+        }
+    if (a->out_rgb) std::memcpy(a->out_rgb, res, (size_t)(3 * n) * sizeof(double));
+    if (a->out_variance) std::memcpy(a->out_variance, vb[a->levels & 1].data(), (size_t)n * sizeof(double));
     return SRT_OK;
 }
 

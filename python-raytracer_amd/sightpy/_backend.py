@@ -246,6 +246,45 @@ def release_buffer(name):
         N.check(lib, lib.srt_device_free(ctx, cur[0]))
 
 
+def _addr(p):
+    """The address in a ctypes pointer or an int."""
+    return p.value if isinstance(p, ctypes.c_void_p) else int(p)
+
+
+class DeviceArrays:
+    """Device allocations of a context for the length of a `with` block (srt_device_alloc), freed at its end on
+    every path."""
+
+    def __init__(self, ctx=None):
+        self.lib = library()
+        self.ctx = context()[1] if ctx is None else ctx
+        self.ptrs = []
+
+    def alloc(self, nbytes):
+        p = ctypes.c_void_p()
+        N.check(self.lib, self.lib.srt_device_alloc(self.ctx, max(int(nbytes), 8), ctypes.byref(p)))
+        self.ptrs.append(p)
+        return p
+
+    def doubles(self, count):
+        return self.alloc(8 * int(count))
+
+    def fetch(self, p, shape, dtype=np.float64):
+        """A host copy of the device array at `p`."""
+        out = np.empty(shape, dtype=dtype)
+        N.check(self.lib, self.lib.srt_memcpy(self.ctx, N.ptr(out), p, out.nbytes))
+        return out
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        ptrs, self.ptrs = self.ptrs, []
+        for p in ptrs:
+            self.lib.srt_device_free(self.ctx, p)
+        return False
+
+
 def numpy_uniforms(n_out, n_skip=0, out=None):
     """`np.random.rand(n_out)` computed on the GPU (then `n_skip` more draws), advancing numpy's
     global RandomState exactly as the host draws would (srt_mt19937_uniforms).
@@ -284,7 +323,8 @@ def _default_seed():
 
 
 def render_scene(scene, spp, jitter=None, seed=None, batch_size=None, rows=None, want_rgb=True, want_hits=False,
-                 jitter_device=None, mt=False, pinned_u8=False, rgbx=False, prefetch=None, out_u8=None):
+                 jitter_device=None, mt=False, pinned_u8=False, rgbx=False, prefetch=None, out_u8=None,
+                 sample_base=0, rgb_device=None, want_u8=True):
     """Scene.render on the device.  `jitter` (spp, 4, H*W) from numpy or None for the device RNG;
     `jitter_device`: the same uniforms already in device memory (numpy_uniforms); `mt=True`: the
     jitter is numpy's global stream generated on the device (the reference's draws, including the
@@ -295,7 +335,11 @@ def render_scene(scene, spp, jitter=None, seed=None, batch_size=None, rows=None,
     (R, G, B, 255; SRT_RENDER_RGBX), srgb8 of shape (rows, W, 4).  `prefetch` (whole frames with
     `mt`): the jitter's generation is queued on the GPU (srt_render_prefetch) before the scene is
     lowered and uploaded, so the two overlap (default on; $SIGHTPY_PREFETCH=0 turns it off).
-    `out_u8`: a host uint8 array of the image's size to write the image into (image_block)."""
+    `out_u8`: a host uint8 array of the image's size to write the image into (image_block).
+    `sample_base`: the frame's index of this call's first sample (its samples are sample_base .. sample_base +
+    spp - 1 of a longer frame: their Monte-Carlo keys and device-RNG jitter; `jitter` / `jitter_device` hold this
+    call's samples only).  `rgb_device`: a device pointer (3 * npix doubles) that receives the linear RGB in place
+    of a host array (result.rgb is None); `want_u8=False`: no uint8 image (result.srgb8 is None)."""
     lib, ctx = context()
     if prefetch is None:
         prefetch = os.environ.get("SIGHTPY_PREFETCH", "1") != "0"
@@ -307,13 +351,13 @@ def render_scene(scene, spp, jitter=None, seed=None, batch_size=None, rows=None,
     cd = camera_desc(cam)
     a = N.RenderArgs()
     a.spp = int(spp)
-    a.sample_base = 0
+    a.sample_base = int(sample_base)
     a.n_rows = nrows
     a.batch_spp = int(batch_size or 0)
     a.rows = N.ptr(rows_arr)
     j = None
     if jitter_device is not None:
-        a.jitter = jitter_device.value if isinstance(jitter_device, ctypes.c_void_p) else jitter_device
+        a.jitter = _addr(jitter_device)
     elif jitter is not None:
         j = np.ascontiguousarray(jitter, dtype=np.float64)
         if j.shape != (spp, 4, npix):
@@ -326,29 +370,33 @@ def render_scene(scene, spp, jitter=None, seed=None, batch_size=None, rows=None,
             raise ValueError("mt=True draws the jitter itself")
         state = N.MtState.from_numpy()
         a.mt = ctypes.pointer(state)
+    if rgb_device is not None:
+        want_rgb = True
     a.flags = (0 if want_rgb else N.RENDER_RGB_LOCAL) | (N.RENDER_RGBX if rgbx else 0)
     # (the prefetch runs before this frame's scene replaces the resident one: not while that one is a
     # per-hit-inputs scene, on which the library refuses it)
     if mt and prefetch and rows_arr is None and nrows == H and not _STATE["scene_inputs"].get(ctx.value):
         N.check(lib, lib.srt_render_prefetch(ctx, ctypes.byref(cd), ctypes.byref(a)))
     upload(scene)
-    rgb = np.empty((3, npix)) if want_rgb else None
+    rgb = np.empty((3, npix)) if want_rgb and rgb_device is None else None
     ch = 4 if rgbx else 3
-    if out_u8 is not None:
+    if not want_u8:
+        u8 = None
+    elif out_u8 is not None:
         if out_u8.dtype != np.uint8 or out_u8.size != ch * npix or not out_u8.flags.c_contiguous:
             raise ValueError("out_u8 must be a contiguous uint8 array of %d bytes" % (ch * npix))
         u8 = out_u8.reshape(npix, ch)
     else:
         u8 = (pinned_buffer("render_u8", ch * npix) if pinned_u8 else np.empty(ch * npix, dtype=np.uint8)).reshape(npix, ch)
     hits = np.empty((spp, npix), dtype=np.int32) if want_hits else None
-    a.out_rgb = N.ptr(rgb)
+    a.out_rgb = N.ptr(rgb) if rgb_device is None else _addr(rgb_device)
     a.out_srgb8 = N.ptr(u8)
     a.out_hit_id = N.ptr(hits)
     st = N.Stats()
     N.check(lib, lib.srt_render(ctx, ctypes.byref(cd), ctypes.byref(a), ctypes.byref(st)))
     if state is not None:
         state.to_numpy()
-    return RenderResult(u8.reshape(nrows, W, ch), rgb, hits, st.as_dict())
+    return RenderResult(None if u8 is None else u8.reshape(nrows, W, ch), rgb, hits, st.as_dict())
 
 
 def render_group(scene, spp, seed=None, batch_size=None, want_rgb=True, mt=True):
@@ -507,18 +555,30 @@ def texture_lookup(u8, repeat, u, v, linear=True):
 
 def denoise_params(spec):
     """Scene.render's `denoise` argument -> the filter's parameters (N.DENOISE_DEFAULTS overridden by a
-    dict), or None for no denoising.  ValueError for an unknown key or a value srt_denoise would refuse."""
+    dict), or None for no denoising.  ValueError for an unknown key or a value srt_denoise would refuse.
+    With "variance" or "demodulate" on, the dict also holds N.DENOISE_VAR_DEFAULTS' keys (the half-frame mode,
+    srt_denoise_var); otherwise it holds srt_denoise's parameters alone."""
     if spec is None or spec is False:
         return None
     params = dict(N.DENOISE_DEFAULTS)
     if spec is True:
         return params
+    known = sorted(list(params) + list(N.DENOISE_VAR_DEFAULTS))
     if not isinstance(spec, dict):
-        raise ValueError("denoise must be a bool or a dict of %s" % sorted(params))
+        raise ValueError("denoise must be a bool or a dict of %s" % known)
+    extra = dict(N.DENOISE_VAR_DEFAULTS)
     for k, v in spec.items():
-        if k not in params:
-            raise ValueError("denoise: unknown key %r (known: %s)" % (k, ", ".join(sorted(params))))
-        if k == "levels":
+        if k not in params and k not in extra:
+            raise ValueError("denoise: unknown key %r (known: %s)" % (k, ", ".join(known)))
+        if k in ("variance", "demodulate"):
+            if not isinstance(v, (bool, np.bool_)):
+                raise ValueError("denoise: %s must be a bool, not %r" % (k, v))
+            extra[k] = bool(v)
+        elif k == "sigma_lum":
+            if isinstance(v, bool) or not float(v) > 0.0 or float(v) == float("inf"):
+                raise ValueError("denoise: %s must be a positive number, not %r" % (k, v))
+            extra[k] = float(v)
+        elif k == "levels":
             if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= N.DENOISE_MAX_LEVELS:
                 raise ValueError("denoise: levels must be an integer in 0..%d, not %r" % (N.DENOISE_MAX_LEVELS, v))
             params[k] = int(v)
@@ -526,6 +586,8 @@ def denoise_params(spec):
             if isinstance(v, bool) or not float(v) > 0.0 or float(v) == float("inf"):
                 raise ValueError("denoise: %s must be a positive number, not %r" % (k, v))
             params[k] = float(v)
+    if extra["variance"] or extra["demodulate"]:
+        params.update(extra)
     return params
 
 
@@ -592,6 +654,136 @@ def denoise(rgb, aovs, width, height, levels=N.DENOISE_DEFAULTS["levels"],
     if timings is not None:
         timings.extend(float(v) for v in ms)
     return out, (None if u8 is None else u8.reshape(H, W, ch))
+
+
+def render_aovs_device(scene, pool):
+    """render_aovs' normal, albedo, position and depth images left in device memory of `pool` (a DeviceArrays):
+    {"normal", "albedo", "position", "depth": device pointers, "ms_kernel"}."""
+    upload(scene, ctx=pool.ctx)
+    cd = camera_desc(scene.camera)
+    n = int(scene.camera.screen_width) * int(scene.camera.screen_height)
+    res = {k: pool.doubles(rows * n) for k, rows in (("normal", 3), ("albedo", 3), ("position", 3), ("depth", 1))}
+    out = N.AovOut()
+    for k, p in res.items():
+        setattr(out, k, p.value)
+    N.check(pool.lib, pool.lib.srt_render_aovs(pool.ctx, ctypes.byref(cd), ctypes.byref(out)))
+    res["ms_kernel"] = float(out.ms_kernel)
+    return res
+
+
+def _sum_stats(a, b):
+    """The stats of a frame rendered as two calls."""
+    out = dict(a)
+    for k in ("total_rays", "shadow_rays", "passes", "ms_wall", "ms_device", "ms_trace_kernels", "ms_primary_kernel",
+              "retries"):
+        out[k] = a[k] + b[k]
+    ra, rb = a["rays_per_depth"], b["rays_per_depth"]
+    out["rays_per_depth"] = [(ra[d] if d < len(ra) else 0) + (rb[d] if d < len(rb) else 0)
+                             for d in range(max(len(ra), len(rb)))]
+    return out
+
+
+def render_halves(scene, spp, rng="numpy", seed=None, batch_size=None, pool=None):
+    """The frame Scene.render(spp) traces, as two half-frames: samples 0 .. ka-1 (ka = spp // 2) and
+    ka .. spp-1 of that very frame -- the same jitter, the same Monte-Carlo keys (sample_base = ka for the
+    second call) -- each averaged over its own samples.  numpy's global RNG is left where the plain render leaves
+    it.  rng="numpy": the whole stream (every sample's jitter, then the sizing draw) is generated once on the
+    device and each call reads its slice.
+    Returns (A, B, ka, kb, stats): with `pool` (a DeviceArrays) A and B are device pointers to (3, n) doubles in
+    it, without it host arrays."""
+    if rng not in ("numpy", "numpy-host", "device"):
+        raise ValueError("rng must be 'numpy', 'numpy-host' or 'device'")
+    spp = int(spp)
+    if spp < 2:
+        raise ValueError("half-frames need at least 2 samples per pixel, not %d" % spp)
+    ka = spp // 2
+    kb = spp - ka
+    cam = scene.camera
+    n = int(cam.screen_width) * int(cam.screen_height)
+    own = DeviceArrays() if pool is None else None
+    p = own if pool is None else pool
+    try:
+        A, B = p.doubles(3 * n), p.doubles(3 * n)
+        halves = ((A, 0, ka), (B, ka, kb))
+        kw = dict(batch_size=batch_size, want_u8=False)
+        if rng == "numpy":
+            # (the seed of the Monte-Carlo draws comes from numpy's state before the jitter, as in render_scene(mt=True))
+            kw["seed"] = seed if seed is not None else _default_seed()
+            try:
+                j = numpy_uniforms(spp * 4 * n, n_skip=4 * n)  # the sizing draw's numbers are skipped (scene.py:81)
+                st = [render_scene(scene, k, jitter_device=j.value + 8 * 4 * n * s0, sample_base=s0, rgb_device=dst, **kw)
+                      .stats for dst, s0, k in halves]
+            finally:
+                release_buffer("uniforms")
+        elif rng == "numpy-host":
+            jitter = cam.draw_jitter(spp)
+            cam.draw_jitter(1)  # reference draws one more get_ray for sizing (scene.py:81)
+            kw["seed"] = seed if seed is not None else _default_seed()  # (after the draws, as the plain render's)
+            st = [render_scene(scene, k, jitter=jitter[s0:s0 + k], sample_base=s0, rgb_device=dst, **kw).stats
+                  for dst, s0, k in halves]
+        else:
+            kw["seed"] = seed if seed is not None else _default_seed()
+            st = [render_scene(scene, k, sample_base=s0, rgb_device=dst, **kw).stats for dst, s0, k in halves]
+        stats = _sum_stats(st[0], st[1])
+        if pool is not None:
+            return A, B, ka, kb, stats
+        return own.fetch(A, (3, n)), own.fetch(B, (3, n)), ka, kb, stats
+    finally:
+        if own is not None:
+            own.__exit__()
+
+
+def denoise_var(rgb_a, rgb_b, spp_a, spp_b, aovs, width, height, variance=False, demodulate=False,
+                levels=N.DENOISE_DEFAULTS["levels"], sigma_color=N.DENOISE_DEFAULTS["sigma_color"],
+                sigma_lum=N.DENOISE_VAR_DEFAULTS["sigma_lum"], sigma_normal=N.DENOISE_DEFAULTS["sigma_normal"],
+                sigma_albedo=N.DENOISE_DEFAULTS["sigma_albedo"], sigma_plane=N.DENOISE_DEFAULTS["sigma_plane"],
+                want_rgb=True, want_variance=False, want_u8=True, rgbx=False, out_u8=None, timings=None, ctx=None):
+    """srt_denoise_var: the a-trous filter over a frame given as two half-frames `rgb_a` (mean of `spp_a`
+    samples) and `rgb_b` (mean of `spp_b`), with the per-pixel variance of their difference steering the colour
+    weight (`variance`, sigma_lum) and / or on the albedo-demodulated colour (`demodulate`); with neither it is
+    denoise() of their sample-weighted mean.  The half-frames and the guides `aovs` ("normal", "albedo",
+    "position", "depth") are numpy arrays or device pointers (ctypes.c_void_p / int: used in place).
+    Returns (filtered rgb (3, n) or None, the last level's variance (n,) or None, uint8 image or None).
+    `timings` receives each level's kernel time, the whole chain's (prepare to the end of the resolve) and the
+    prepare kernel's, ms by HIP events."""
+    lib = library()
+    if ctx is None:
+        ctx = context()[1]
+    W, H = int(width), int(height)
+    n = W * H
+    a = N.DenoiseVarArgs()
+    keep = []
+    for field, v, rows in (("rgb_a", rgb_a, 3), ("rgb_b", rgb_b, 3), ("normal", aovs["normal"], 3),
+                           ("albedo", aovs["albedo"], 3), ("position", aovs["position"], 3), ("depth", aovs["depth"], 1)):
+        if isinstance(v, (ctypes.c_void_p, int)):
+            setattr(a, field, _addr(v))
+            continue
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        if v.size != rows * n:
+            raise ValueError("denoise_var: %s must hold %d x %d values" % (field, rows, n))
+        keep.append(v)
+        setattr(a, field, N.ptr(v))
+    a.spp_a, a.spp_b, a.levels = int(spp_a), int(spp_b), int(levels)
+    a.flags = (N.DENOISE_RGBX if rgbx else 0) | (N.DENOISE_VARIANCE if variance else 0) | \
+              (N.DENOISE_DEMODULATE if demodulate else 0)
+    a.sigma_color, a.sigma_lum, a.sigma_normal = float(sigma_color), float(sigma_lum), float(sigma_normal)
+    a.sigma_albedo, a.sigma_plane = float(sigma_albedo), float(sigma_plane)
+    out = np.empty((3, n)) if want_rgb else None
+    var = np.empty(n) if want_variance else None
+    ch = 4 if rgbx else 3
+    u8 = None
+    if out_u8 is not None:
+        if out_u8.dtype != np.uint8 or out_u8.size != ch * n or not out_u8.flags.c_contiguous:
+            raise ValueError("out_u8 must be a contiguous uint8 array of %d bytes" % (ch * n))
+        u8 = out_u8.reshape(n, ch)
+    elif want_u8:
+        u8 = np.empty((n, ch), dtype=np.uint8)
+    ms = np.zeros(max(a.levels, 0) + 2) if timings is not None else None
+    a.out_rgb, a.out_variance, a.out_srgb8, a.ms_levels = N.ptr(out), N.ptr(var), N.ptr(u8), N.ptr(ms)
+    N.check(lib, lib.srt_denoise_var(ctx, W, H, ctypes.byref(a)))
+    if timings is not None:
+        timings.extend(float(v) for v in ms)
+    return out, var, (None if u8 is None else u8.reshape(H, W, ch))
 
 
 def primary_rays(camera, jitter):

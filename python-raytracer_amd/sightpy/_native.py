@@ -278,10 +278,38 @@ class DenoiseArgs(ctypes.Structure):
     ]
 
 
-DENOISE_RGBX = 2  # SRT_DENOISE_*
+class DenoiseVarArgs(ctypes.Structure):
+    """srt_denoise_var_args."""
+    _fields_ = [
+        ("rgb_a", _p),
+        ("rgb_b", _p),
+        ("spp_a", ctypes.c_int32),
+        ("spp_b", ctypes.c_int32),
+        ("normal", _p),
+        ("albedo", _p),
+        ("position", _p),
+        ("depth", _p),
+        ("levels", ctypes.c_int32),
+        ("flags", ctypes.c_int32),
+        ("sigma_color", ctypes.c_double),
+        ("sigma_lum", ctypes.c_double),
+        ("sigma_normal", ctypes.c_double),
+        ("sigma_albedo", ctypes.c_double),
+        ("sigma_plane", ctypes.c_double),
+        ("out_rgb", _p),
+        ("out_variance", _p),
+        ("out_srgb8", _p),
+        ("ms_levels", _p),
+    ]
+
+
+DENOISE_RGBX, DENOISE_VARIANCE, DENOISE_DEMODULATE = 2, 4, 8  # SRT_DENOISE_*
 DENOISE_MAX_LEVELS = 8
 # srt_denoise's defaults (Scene.render(denoise=True)); untuned beyond 64-128 px cornell frames
 DENOISE_DEFAULTS = {"levels": 4, "sigma_color": 1.0, "sigma_normal": 0.35, "sigma_albedo": 0.1, "sigma_plane": 0.02}
+# what Scene.render(denoise={...}) takes beside them: the half-frame mode of srt_denoise_var (either flag
+# turns it on; sigma_lum replaces sigma_color when `variance` is on)
+DENOISE_VAR_DEFAULTS = {"variance": False, "demodulate": False, "sigma_lum": 1.0}
 
 # name -> (restype, argtypes) for every entry point of include/sightpy_rt.h
 RENDER_ASYNC, RENDER_SHARDED, RENDER_GATHER_RGB, RENDER_RGB_ROWS, RENDER_RGB_LOCAL, RENDER_RGBX = 1, 2, 4, 8, 16, 32  # SRT_RENDER_*
@@ -309,6 +337,7 @@ SIGNATURES = {
     "srt_primary_rays": (ctypes.c_int, [_p, ctypes.POINTER(CameraDesc), _p, _p, _p]),
     "srt_render_aovs": (ctypes.c_int, [_p, ctypes.POINTER(CameraDesc), ctypes.POINTER(AovOut)]),
     "srt_denoise": (ctypes.c_int, [_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(DenoiseArgs)]),
+    "srt_denoise_var": (ctypes.c_int, [_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(DenoiseVarArgs)]),
     "srt_mt19937_uniforms": (ctypes.c_int, [_p, _p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, _p, _p,
                                             ctypes.POINTER(ctypes.c_int32)]),
     "srt_device_alloc": (ctypes.c_int, [_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p)]),

@@ -94,11 +94,22 @@ class Scene:
         before anything runs).  The samples are drawn and traced exactly as without it, and numpy's
         RNG is left in the same state.  Not available for a scene with user subclasses
         (NotImplementedError).
+
+        The dict's `"variance": True` and `"demodulate": True` (independent, both off by default) select the
+        half-frame mode (srt_denoise_var): the same samples are traced as two half-frames, samples
+        0 .. spp//2 - 1 and the rest.  `variance` takes a per-pixel noise estimate from their difference and
+        weighs colour differences against it (`"sigma_lum"`, default 1, in place of `sigma_color`): an edge
+        the guides do not see survives where the frame is clean, and strong noise is still averaged.
+        `demodulate` filters colour / albedo and multiplies the albedo back, which keeps texture detail.
+        Half-frames, guides and the filter's planes stay in device memory; only the uint8 image is copied
+        out.  Needs spp >= 2 (ValueError) and a single GPU (NotImplementedError with several selected).
         """
         from . import _backend as B
         from . import _hybrid
 
         dn = B.denoise_params(denoise)
+        if dn is not None and "variance" in dn:
+            return self._render_denoised_halves(samples_per_pixel, batch_size, rng, seed, dn)
         if dn is not None:
             return self._render_denoised(samples_per_pixel, batch_size, rng, seed, dn)
         print("Rendering...")
@@ -175,6 +186,40 @@ class Scene:
         _, u8 = B.denoise(out.rgb, aovs, W, H, rgbx=True, out_u8=blk, timings=ms, ctx=ctx, **params)
         self.last_stats = dict(out.stats, denoise=dict(params, ms_aov_kernel=aovs["ms_kernel"], ms_levels=ms[:-1],
                                                             ms_filter=ms[-1]))
+        print("Render Took", time.time() - t0)
+        return B.rgb_image(u8, W, H, mapped=blk is not None)
+
+    def _render_denoised_halves(self, samples_per_pixel, batch_size, rng, seed, params):
+        """render(denoise={"variance" / "demodulate": True, ...}): the frame as two half-frames
+        (_backend.render_halves), the guide images and srt_denoise_var, all in device memory of the context;
+        the image is the filter's own resolve into the pinned image block."""
+        from . import _backend as B
+        from . import _hybrid
+
+        if rng not in ("numpy", "numpy-host", "device"):
+            raise ValueError("rng must be 'numpy', 'numpy-host' or 'device'")
+        if int(samples_per_pixel) < 2:
+            raise ValueError("denoise: variance / demodulate split the frame into two half-frames and need "
+                             "samples_per_pixel >= 2, not %r" % (samples_per_pixel,))
+        if _hybrid.is_hybrid(self):
+            raise NotImplementedError("denoise: a scene with user Collider / Material / texture / Light subclasses "
+                                      "is shaded through the host; its guide images are not computed on the device")
+        if len(B.devices()) > 1:
+            raise NotImplementedError("denoise: variance / demodulate render on one GPU; %d are selected "
+                                      "($SIGHTPY_DEVICES)" % len(B.devices()))
+        print("Rendering...")
+        t0 = time.time()
+        H, W = int(self.camera.screen_height), int(self.camera.screen_width)
+        with B.DeviceArrays() as pool:
+            A, Bh, ka, kb, stats = B.render_halves(self, samples_per_pixel, rng=rng, seed=seed, batch_size=batch_size,
+                                                   pool=pool)
+            aovs = B.render_aovs_device(self, pool)
+            blk = B.image_block(4 * W * H)
+            ms = []
+            _, _, u8 = B.denoise_var(A, Bh, ka, kb, aovs, W, H, want_rgb=False, rgbx=True, out_u8=blk, timings=ms,
+                                     **params)
+        self.last_stats = dict(stats, denoise=dict(params, ka=ka, kb=kb, ms_aov_kernel=aovs["ms_kernel"],
+                                                   ms_levels=ms[:-2], ms_filter=ms[-2], ms_prepare=ms[-1]))
         print("Render Took", time.time() - t0)
         return B.rgb_image(u8, W, H, mapped=blk is not None)
 
