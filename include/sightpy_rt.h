@@ -32,6 +32,8 @@
  *   srt_render_aovs, srt_denoise, srt_denoise_var: no counterpart (first-hit guide images and the a-trous
  *                             filter that denoises a low-sample frame with them; _var: from two half-frames,
  *                             with their difference as the per-pixel noise estimate)
+ *   srt_temporal_accumulate: no counterpart (the half-frames of an animation's frame blended with the
+ *                             reprojected half-frames accumulated over the earlier frames)
  *   srt_upload_scene       <- (scene lowering; the reference deep-copies the Scene per task,
  *                              scene.py:85)
  *
@@ -546,6 +548,62 @@ typedef struct srt_denoise_var_args {
                                resolve), then the prepare kernel alone (HIP events), or NULL */
 } srt_denoise_var_args;
 int srt_denoise_var(srt_ctx* ctx, int32_t width, int32_t height, const srt_denoise_var_args* args);
+
+/* srt_temporal_accumulate: blend the two half-frames of the current frame with the reprojected, accumulated
+ * half-frames of the previous frames, each half with its own history (so the halves stay independent and
+ * srt_denoise_var's variance estimate from their difference stays valid); srt_denoise_var then runs on out_a /
+ * out_b as on any two half-frames.  All float64, in the order written; primes mark prev_cam.  Per pixel p with
+ * A = rgb_a, B = rgb_b, guides hit_id_p, x_p = position, n_p = normal, t_p = depth:
+ *   ok = p is not background (n_p != 0) and A, B are finite
+ *   d = max(albedo, 1e-3) per channel with SRT_TEMPORAL_DEMODULATE, else 1;  uA = A / d, uB = B / d
+ *   not ok:  out_a = A, out_b = B, out_hist_a = A, out_hist_b = B, out_len = 0
+ *   e = x_p - look_from', fwd' = fwd_fd' / focal_distance', zc = e . fwd', xc = (e . right') / zc,
+ *   yc = (e . up') / zc, fx = W > 1 ? ((xc + cw'/2) / cw') * (W-1) : 0, fy = H > 1 ? ((ch'/2 - yc) / ch') * (H-1) : 0
+ *   no history unless zc > 0, -1 < fx < W, -1 < fy < H
+ *   x0 = floor(fx), y0 = floor(fy), ax = fx - x0, ay = fy - y0; taps (y0, x0), (y0, x0+1), (y0+1, x0), (y0+1, x0+1)
+ *   with the bilinear weights w; tap q counts when it is inside the image, w > 0, hist_len_q >= 1,
+ *   hist_hit_id_q == hit_id_p, |n_p - n_q|^2 <= normal_max and |n_p . (x_q - x_p)| / t_p <= plane_max
+ *   sw = sum(w); history exists when sw >= 0.01: hA = sum(w * hist_a_q) / sw, hB likewise, L = sum(w * hist_len_q) / sw
+ *   with history:    N = min(L + 1, max_history), alpha = 1 / N, uA' = hA + alpha * (uA - hA), uB' likewise;
+ *                    out_len = N, out_hist_a/b = uA'/uB', out_a/b = uA' * d / uB' * d
+ *   without history: out_a = A, out_b = B (bit for bit), out_hist_a/b = uA/uB, out_len = 1
+ * hist_len == NULL: the first frame, no history (the other hist_* pointers and prev_cam are not read).  The
+ * caller keeps the current hit_id / position / normal as the next call's hist_hit_id / hist_position /
+ * hist_normal, with out_hist_a / out_hist_b / out_len and the current camera.  Pointers may address host or
+ * device memory (device arrays are used and written in place); out_a / out_b may be rgb_a / rgb_b themselves,
+ * the out_hist_* arrays must not be the hist_* arrays.  Needs no scene.
+ * SRT_ERR_ARG: a non-positive size, max_history < 1, a negative or non-finite normal_max / plane_max, an unknown
+ * flag, a NULL rgb_a / rgb_b / hit_id / position / normal / depth or output, a NULL albedo with DEMODULATE,
+ * hist_len given with another hist_* pointer or prev_cam NULL, prev_cam of another width or height, out_hist_a/b
+ * / out_len equal to hist_a/b / hist_len. */
+#define SRT_TEMPORAL_DEMODULATE 1 /* accumulate colour / max(albedo, 1e-3); out_a / out_b are multiplied back */
+typedef struct srt_temporal_args {
+    const double* rgb_a;         /* [3][n] half-frame A of the current frame, linear RGB */
+    const double* rgb_b;         /* [3][n] half-frame B */
+    const int32_t* hit_id;       /* [n]    the current frame's guides (srt_render_aovs) */
+    const double* position;      /* [3][n] */
+    const double* normal;        /* [3][n] */
+    const double* albedo;        /* [3][n], or NULL without SRT_TEMPORAL_DEMODULATE */
+    const double* depth;         /* [n] */
+    const srt_camera* prev_cam;  /* the previous frame's camera (xs / ys are not read and may be NULL), or NULL */
+    const double* hist_a;        /* [3][n] the previous call's out_hist_a */
+    const double* hist_b;        /* [3][n] the previous call's out_hist_b */
+    const double* hist_len;      /* [n]    the previous call's out_len, or NULL: no history */
+    const int32_t* hist_hit_id;  /* [n]    the previous frame's guides */
+    const double* hist_position; /* [3][n] */
+    const double* hist_normal;   /* [3][n] */
+    int32_t max_history;         /* >= 1: the accumulated length is clamped to it (alpha >= 1 / max_history) */
+    int32_t flags;               /* SRT_TEMPORAL_DEMODULATE */
+    double normal_max;           /* >= 0: largest |n_p - n_q|^2 of a tap */
+    double plane_max;            /* >= 0: largest |n_p . (x_q - x_p)| / t_p of a tap */
+    double* out_a;               /* [3][n] accumulated half-frame A */
+    double* out_b;               /* [3][n] accumulated half-frame B */
+    double* out_hist_a;          /* [3][n] the next call's hist_a (demodulated with the flag) */
+    double* out_hist_b;          /* [3][n] */
+    double* out_len;             /* [n]    the next call's hist_len */
+    double* ms_kernel;           /* host: duration of the kernel (HIP events), or NULL */
+} srt_temporal_args;
+int srt_temporal_accumulate(srt_ctx* ctx, int32_t width, int32_t height, const srt_temporal_args* args);
 /* numpy's legacy global-RNG stream on the device: writes the n_out doubles that
  * `np.random.rand(n_out)` would return for the RandomState with MT19937 key[624] and position
  * pos (0..624, as in np.random.get_state()), then consumes n_skip more draws, and returns the

@@ -1,6 +1,7 @@
 // rt_api_entry.h -- entry points of one kernel each: srt_nearest, srt_intersect_collider,
 // srt_collider_surface, srt_texture_lookup, srt_material_normal, srt_primary_rays; the first-hit AOVs and
-// the denoiser (srt_render_aovs, srt_denoise, srt_denoise_var; kernels in rt_denoise.h); device memory for the caller
+// the denoiser (srt_render_aovs, srt_denoise, srt_denoise_var, srt_temporal_accumulate; kernels in rt_denoise.h);
+// device memory for the caller
 // (srt_device_alloc, srt_device_free, srt_memcpy); srt_mt19937_uniforms.
 // At its head, what only these entry points use: run_kernel, EventList, stage_in.
 // A fragment of rt_kernels.hip, included at its end and not compiled alone.  Before it: what stands above
@@ -428,6 +429,83 @@ int srt_denoise_var(srt_ctx* c, int32_t width, int32_t height, const srt_denoise
     if (a->out_rgb) HIP_TRY(bufs.copy(a->out_rgb, (const double*)res, 3 * n));
     if (a->out_variance) HIP_TRY(bufs.copy(a->out_variance, (const double*)vb[a->levels & 1], n));
     if (a->out_srgb8 && du8 != a->out_srgb8) HIP_TRY(bufs.copy(a->out_srgb8, (const uint8_t*)du8, u8_bytes));
+    return SRT_OK;
+}
+
+int srt_temporal_accumulate(srt_ctx* c, int32_t width, int32_t height, const srt_temporal_args* a) {
+    if (!c || !a) return fail(SRT_ERR_ARG, "null argument");
+    if (width <= 0 || height <= 0) return fail(SRT_ERR_ARG, "srt_temporal_accumulate: non-positive image size");
+    if (a->max_history < 1) return fail(SRT_ERR_ARG, "srt_temporal_accumulate: max_history must be at least 1");
+    if (!(a->normal_max >= 0.0) || !(a->plane_max >= 0.0) || a->normal_max - a->normal_max != 0.0 ||
+        a->plane_max - a->plane_max != 0.0)
+        return fail(SRT_ERR_ARG, "srt_temporal_accumulate: normal_max and plane_max must be finite and not negative");
+    if (a->flags & ~SRT_TEMPORAL_DEMODULATE) return fail(SRT_ERR_ARG, "srt_temporal_accumulate: unknown flag");
+    const bool demod = (a->flags & SRT_TEMPORAL_DEMODULATE) != 0;
+    if (!a->rgb_a || !a->rgb_b || !a->hit_id || !a->position || !a->normal || !a->depth || (demod && !a->albedo))
+        return fail(SRT_ERR_ARG, "srt_temporal_accumulate: NULL half-frame or guide array");
+    if (!a->out_a || !a->out_b || !a->out_hist_a || !a->out_hist_b || !a->out_len)
+        return fail(SRT_ERR_ARG, "srt_temporal_accumulate: NULL output");
+    if (a->hist_len) {
+        if (!a->hist_a || !a->hist_b || !a->hist_hit_id || !a->hist_position || !a->hist_normal || !a->prev_cam)
+            return fail(SRT_ERR_ARG, "srt_temporal_accumulate: hist_len without the other history arrays or prev_cam");
+        if (a->prev_cam->width != width || a->prev_cam->height != height)
+            return fail(SRT_ERR_ARG, "srt_temporal_accumulate: prev_cam is of another size");
+        if (a->out_hist_a == a->hist_a || a->out_hist_b == a->hist_b || a->out_len == a->hist_len)
+            return fail(SRT_ERR_ARG, "srt_temporal_accumulate: the history cannot be updated in place");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    DevList bufs;
+    const int64_t n = (int64_t)width * height;
+    TemporalPlanes T{};
+    T.npix = n;
+    T.W = width, T.H = height;
+    T.max_history = (double)a->max_history, T.normal_max = a->normal_max, T.plane_max = a->plane_max;
+    T.demod = demod ? 1 : 0;
+    HIP_TRY(stage_in(bufs, a->rgb_a, 3 * n, &T.a));
+    HIP_TRY(stage_in(bufs, a->rgb_b, 3 * n, &T.b));
+    HIP_TRY(stage_in(bufs, a->hit_id, n, &T.hit_id));
+    HIP_TRY(stage_in(bufs, a->position, 3 * n, &T.position));
+    HIP_TRY(stage_in(bufs, a->normal, 3 * n, &T.normal));
+    if (demod) HIP_TRY(stage_in(bufs, a->albedo, 3 * n, &T.albedo));
+    HIP_TRY(stage_in(bufs, a->depth, n, &T.depth));
+    if (a->hist_len) {
+        T.cam = temporal_cam(*a->prev_cam);
+        HIP_TRY(stage_in(bufs, a->hist_a, 3 * n, &T.hist_a));
+        HIP_TRY(stage_in(bufs, a->hist_b, 3 * n, &T.hist_b));
+        HIP_TRY(stage_in(bufs, a->hist_len, n, &T.hist_len));
+        HIP_TRY(stage_in(bufs, a->hist_hit_id, n, &T.hist_hit_id));
+        HIP_TRY(stage_in(bufs, a->hist_position, 3 * n, &T.hist_position));
+        HIP_TRY(stage_in(bufs, a->hist_normal, 3 * n, &T.hist_normal));
+    }
+    // an output in device memory is written in place, a host array through a buffer of the call
+    double* const host[5] = {a->out_a, a->out_b, a->out_hist_a, a->out_hist_b, a->out_len};
+    const int64_t count[5] = {3 * n, 3 * n, 3 * n, 3 * n, n};
+    double* dev[5];
+    for (int k = 0; k < 5; ++k) {
+        if (is_device_ptr(host[k]))
+            dev[k] = host[k];
+        else
+            HIP_TRY(bufs.alloc(&dev[k], count[k]));
+    }
+    const TemporalOut out{dev[0], dev[1], dev[2], dev[3], dev[4]};
+    EventList ev;
+    HIP_TRY(ev.create(2));
+    hipStream_t st = c->f->stream;
+    // one 64-pixel row segment per wave, no grid-stride loop (k_temporal)
+    const int64_t items = (((int64_t)width + 63) / 64) * height, blocks = (items + DN_BLOCK / 64 - 1) / (DN_BLOCK / 64);
+    if (blocks > 0x7fffffff) return fail(SRT_ERR_ARG, "srt_temporal_accumulate: image too large");
+    HIP_TRY(hipEventRecord(ev.e[0], st));
+    hipLaunchKernelGGL(k_temporal, dim3((unsigned)blocks), dim3(DN_BLOCK), 0, st, T, out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev.e[1], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (a->ms_kernel) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+        *a->ms_kernel = ms;
+    }
+    for (int k = 0; k < 5; ++k)
+        if (dev[k] != host[k]) HIP_TRY(bufs.copy(host[k], (const double*)dev[k], count[k]));
     return SRT_OK;
 }
 

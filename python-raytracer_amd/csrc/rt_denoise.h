@@ -51,6 +51,31 @@
 //     a pixel that is copied through keeps its v
 //   finish (k_dn_finish, with DEMODULATE): c' = u' * d where prepare divided, else u' itself (which is c,
 //     bit for bit, on background and non-finite pixels); resolved by resolve_pixel
+//
+// Temporal accumulation (srt_temporal_accumulate, k_temporal; tests/temporal_ref.py restates it).  It runs before
+// prepare: half-frames A, B in, half-frames out_a, out_b out, each blended with its own reprojected history (A's
+// history never mixes with B's, so the two stay independent estimates and v above stays a valid noise estimate).
+// Pixel p of the current frame has guides hit_id_p, x_p (position), n_p (normal), albedo, t_p (depth); the previous
+// call left hist_a, hist_b (the accumulated, demodulated half-frames), hist_len (accumulated frames, a double) and
+// its own hit_id / position / normal; primes mark the previous frame's camera.  hist_len == NULL: no history.
+//   ok = p is not background and A, B are finite (dn_halves_ok)
+//   d = dn_divisor(albedo) with SRT_TEMPORAL_DEMODULATE, else 1;  uA = A / d, uB = B / d per channel
+//   not ok: out_a = A, out_b = B (bit for bit), out_hist_a = A, out_hist_b = B, out_len = 0
+//   projection: e = x_p - look_from', fwd' = fwd_fd' / focal_distance' per component, zc = dot(e, fwd'),
+//     xc = dot(e, right') / zc, yc = dot(e, up') / zc
+//     fx = W > 1 ? ((xc + cw'/2) / cw') * (W-1) : 0,  fy = H > 1 ? ((ch'/2 - yc) / ch') * (H-1) : 0
+//     (the inverse of np.linspace(-cw/2, cw/2, W) / linspace(ch/2, -ch/2, H))
+//     no history unless zc > 0, -1 < fx < W and -1 < fy < H (NaN fails these tests)
+//   taps: x0 = floor(fx), y0 = floor(fy), ax = fx - x0, ay = fy - y0; in this order (y0, x0) with
+//     w = (1-ax)(1-ay), (y0, x0+1) with ax(1-ay), (y0+1, x0) with (1-ax)ay, (y0+1, x0+1) with ax*ay
+//     tap q is valid when it is inside the image, w > 0, hist_len_q >= 1, hist_hit_id_q == hit_id_p,
+//     |n_p - n_q|^2 <= normal_max and |dot(n_p, x_q - x_p)| / t_p <= plane_max
+//     sw = sum(w) over the valid taps; history exists when sw >= 0.01
+//     hA = sum(w * hist_a_q) / sw, hB likewise, L = sum(w * hist_len_q) / sw
+//   with history: N = min(L + 1, max_history), alpha = 1 / N, uA' = hA + alpha * (uA - hA), uB' likewise;
+//     out_len = N, out_hist_a/b = uA'/uB', out_a/b = uA' * d / uB' * d (uA' / uB' themselves without DEMODULATE)
+//   without (a disocclusion included): out_a = A, out_b = B (bit for bit), out_hist_a/b = uA/uB, out_len = 1
+// The current frame's hit_id / position / normal are the next call's history guides; the caller keeps them.
 #ifndef RT_DENOISE_H
 #define RT_DENOISE_H
 
@@ -126,6 +151,8 @@ struct AtrousVar {
     double sl;        // sigma_lum
 };
 
+// pixel i of a planar [3][n] image
+RT_HDM d3 dn_ld3(const double* p, int64_t n, int64_t i) { return d3{p[i], p[n + i], p[2 * n + i]}; }
 RT_HD bool dn_finite(double v) { return v - v == 0.0; }
 RT_HD bool dn_finite3(d3 v) { return dn_finite(v.x) && dn_finite(v.y) && dn_finite(v.z); }
 RT_HD double dn_sq(d3 v) { return (v.x * v.x + v.y * v.y) + v.z * v.z; }
@@ -241,6 +268,105 @@ RT_HD d3 dn_finish_pixel(d3 u, d3 A, d3 B, d3 n, d3 alb) {
     return mul(u, dn_divisor(alb));
 }
 
+// ---- temporal accumulation (header comment) -----------------------------------------------------------
+// the previous frame's camera: srt_camera's scalars, fwd = fwd_fd / focal_distance per component
+struct TemporalCam {
+    d3 from, right, up, fwd;
+    double cw, ch;
+};
+
+RT_HD TemporalCam temporal_cam(const srt_camera& c) {
+    TemporalCam t;
+    t.from = ld3(c.look_from);
+    t.right = ld3(c.right);
+    t.up = ld3(c.up);
+    t.fwd = d3{c.fwd_fd[0] / c.focal_distance, c.fwd_fd[1] / c.focal_distance, c.fwd_fd[2] / c.focal_distance};
+    t.cw = c.cam_width;
+    t.ch = c.cam_height;
+    return t;
+}
+
+// the planes in global memory, planar [3][npix] or [npix], rows of W pixels
+struct TemporalPlanes {
+    const double *a, *b;  // the current half-frames
+    const int32_t* hit_id;
+    const double *position, *normal, *albedo, *depth;
+    const double *hist_a, *hist_b, *hist_len;  // hist_len == NULL: no history
+    const int32_t* hist_hit_id;
+    const double *hist_position, *hist_normal;
+    int64_t npix;
+    int32_t W, H;
+    TemporalCam cam;
+    double max_history, normal_max, plane_max;
+    int32_t demod;
+};
+
+struct TemporalPixel {
+    d3 a, b, hist_a, hist_b;
+    double len;
+};
+
+RT_HD d3 tp_div3(d3 a, d3 d) { return d3{a.x / d.x, a.y / d.y, a.z / d.z}; }
+
+RT_HD TemporalPixel temporal_pixel(const TemporalPlanes& T, int32_t x, int32_t y) {
+    const int64_t n = T.npix, ip = (int64_t)y * T.W + x;
+    const d3 A = dn_ld3(T.a, n, ip), B = dn_ld3(T.b, n, ip), nrm = dn_ld3(T.normal, n, ip);
+    TemporalPixel r;
+    r.a = r.hist_a = A;
+    r.b = r.hist_b = B;
+    r.len = 0.0;
+    if (!dn_halves_ok(A, B, nrm)) return r;
+    d3 d = d3{1.0, 1.0, 1.0};
+    if (T.demod) {
+        d = dn_divisor(dn_ld3(T.albedo, n, ip));
+        r.hist_a = tp_div3(A, d);
+        r.hist_b = tp_div3(B, d);
+    }
+    r.len = 1.0;
+    if (!T.hist_len) return r;
+    const d3 xp = dn_ld3(T.position, n, ip);
+    const d3 e = sub(xp, T.cam.from);
+    const double zc = dot(e, T.cam.fwd);
+    const double xc = dot(e, T.cam.right) / zc, yc = dot(e, T.cam.up) / zc;
+    const double fx = T.W > 1 ? ((xc + T.cam.cw / 2.0) / T.cam.cw) * (double)(T.W - 1) : 0.0;
+    const double fy = T.H > 1 ? ((T.cam.ch / 2.0 - yc) / T.cam.ch) * (double)(T.H - 1) : 0.0;
+    if (!(zc > 0.0 && fx > -1.0 && fx < (double)T.W && fy > -1.0 && fy < (double)T.H)) return r;
+    const double xf = floor(fx), yf = floor(fy);
+    const double ax = fx - xf, ay = fy - yf;
+    const int32_t x0 = (int32_t)xf, y0 = (int32_t)yf;
+    const int32_t id = T.hit_id[ip];
+    const double tp = T.depth[ip];
+    const double wt[4] = {(1.0 - ax) * (1.0 - ay), ax * (1.0 - ay), (1.0 - ax) * ay, ax * ay};
+    double sw = 0.0, L = 0.0;
+    d3 hA = d3{0.0, 0.0, 0.0}, hB = d3{0.0, 0.0, 0.0};
+    for (int k = 0; k < 4; ++k) {
+        const int32_t qx = x0 + (k & 1), qy = y0 + (k >> 1);
+        const double w = wt[k];
+        if (qx < 0 || qx >= T.W || qy < 0 || qy >= T.H || !(w > 0.0)) continue;
+        const int64_t q = (int64_t)qy * T.W + qx;
+        const double lq = T.hist_len[q];
+        if (!(lq >= 1.0) || T.hist_hit_id[q] != id) continue;
+        if (!(dn_sq(sub(nrm, dn_ld3(T.hist_normal, n, q))) <= T.normal_max)) continue;
+        if (!(fabs(dot(nrm, sub(dn_ld3(T.hist_position, n, q), xp))) / tp <= T.plane_max)) continue;
+        sw += w;
+        hA = add(hA, mul(dn_ld3(T.hist_a, n, q), w));
+        hB = add(hB, mul(dn_ld3(T.hist_b, n, q), w));
+        L += w * lq;
+    }
+    if (!(sw >= 0.01)) return r;
+    hA = divs(hA, sw);
+    hB = divs(hB, sw);
+    L = L / sw;
+    const double N = L + 1.0 < T.max_history ? L + 1.0 : T.max_history;
+    const double alpha = 1.0 / N;
+    r.hist_a = add(hA, mul(sub(r.hist_a, hA), alpha));
+    r.hist_b = add(hB, mul(sub(r.hist_b, hB), alpha));
+    r.len = N;
+    r.a = T.demod ? mul(r.hist_a, d) : r.hist_a;
+    r.b = T.demod ? mul(r.hist_b, d) : r.hist_b;
+    return r;
+}
+
 // out_srgb8 of one pixel: resolve_pixel, k_resolve's rule
 RT_HD uint32_t denoise_resolve(d3 c) {
     uint8_t px[3];
@@ -296,8 +422,6 @@ __global__ __launch_bounds__(DN_BLOCK) void k_atrous(AtrousPlanes G, AtrousLevel
     }
 }
 
-RT_HDM d3 dn_ld3(const double* p, int64_t n, int64_t i) { return d3{p[i], p[n + i], p[2 * n + i]}; }
-
 // u and v of the half-frames (header comment); `v` may be NULL (no SRT_DENOISE_VARIANCE).  One thread per
 // pixel, streaming: 12 planes in, 3 or 4 out
 __global__ __launch_bounds__(DN_BLOCK) void k_dn_prepare(DnHalves F, const double* normal, const double* albedo, int64_t n,
@@ -331,6 +455,37 @@ __global__ __launch_bounds__(DN_BLOCK) void k_dn_finish(DnHalves F, const double
             u8[3 * i + 2] = (uint8_t)(px >> 16);
         }
     }
+}
+
+struct TemporalOut {
+    double *a, *b, *hist_a, *hist_b;  // [3][npix] each
+    double* len;                      // [npix]
+};
+
+// Temporal accumulation of the two half-frames (header comment).  Work items as in k_atrous: a wave takes 64
+// consecutive pixels of one row, so the streaming reads and the 13 planar stores are coalesced, and the four
+// gathered history taps of neighbouring lanes fall in the same one or two row segments of the previous frame.
+// One item per wave and no grid-stride loop (the grid is ceil(items / waves per block) blocks): with the loop the
+// 18 plane pointers and the camera stay live across it and 88 SGPRs spill; without it none does
+// (profiles/temporal_resource_usage.txt).  No LDS, no atomics.  out.a / out.b may be the planes T.a / T.b
+// themselves (a pixel reads only its own A, B); the out.hist_* planes must not be the T.hist_* planes, which
+// other pixels gather from.
+__global__ __launch_bounds__(DN_BLOCK) void k_temporal(TemporalPlanes T, TemporalOut out) {
+    const int64_t segs = (T.W + 63) / 64, items = segs * T.H;
+    constexpr int WAVES = DN_BLOCK / 64;
+    const int64_t it = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    if (it >= items) return;
+    const int64_t y = it / segs;
+    const int64_t x = (it - y * segs) * 64 + (threadIdx.x & 63);
+    if (x >= T.W) return;
+    const int64_t n = T.npix;
+    const TemporalPixel r = temporal_pixel(T, (int32_t)x, (int32_t)y);
+    const int64_t ip = y * T.W + x;
+    out.a[ip] = r.a.x; out.a[n + ip] = r.a.y; out.a[2 * n + ip] = r.a.z;
+    out.b[ip] = r.b.x; out.b[n + ip] = r.b.y; out.b[2 * n + ip] = r.b.z;
+    out.hist_a[ip] = r.hist_a.x; out.hist_a[n + ip] = r.hist_a.y; out.hist_a[2 * n + ip] = r.hist_a.z;
+    out.hist_b[ip] = r.hist_b.x; out.hist_b[n + ip] = r.hist_b.y; out.hist_b[2 * n + ip] = r.hist_b.z;
+    out.len[ip] = r.len;
 }
 
 // out_srgb8 of the filtered frame: [n][3], or [n][4] (R, G, B, 255) with SRT_DENOISE_RGBX

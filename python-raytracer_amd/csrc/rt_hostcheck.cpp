@@ -464,6 +464,46 @@ int hc_denoise_var(int32_t width, int32_t height, const srt_denoise_var_args* a)
     return SRT_OK;
 }
 
+// srt_temporal_accumulate: k_temporal's temporal_pixel over host arrays (the outputs may be rgb_a / rgb_b; they
+// must not be the history arrays)
+int hc_temporal(int32_t width, int32_t height, const srt_temporal_args* a) {
+    const bool demod = (a->flags & SRT_TEMPORAL_DEMODULATE) != 0;
+    if (width <= 0 || height <= 0 || a->max_history < 1 || !(a->normal_max >= 0.0) || !(a->plane_max >= 0.0) ||
+        a->normal_max - a->normal_max != 0.0 || a->plane_max - a->plane_max != 0.0 ||
+        (a->flags & ~SRT_TEMPORAL_DEMODULATE) || !a->rgb_a || !a->rgb_b || !a->hit_id || !a->position || !a->normal ||
+        !a->depth || (demod && !a->albedo) || !a->out_a || !a->out_b || !a->out_hist_a || !a->out_hist_b || !a->out_len ||
+        (a->hist_len && (!a->hist_a || !a->hist_b || !a->hist_hit_id || !a->hist_position || !a->hist_normal ||
+                         !a->prev_cam || a->prev_cam->width != width || a->prev_cam->height != height ||
+                         a->out_hist_a == a->hist_a || a->out_hist_b == a->hist_b || a->out_len == a->hist_len))) {
+        g_err = "hc_temporal: bad argument";
+        return SRT_ERR_ARG;
+    }
+    const int64_t n = (int64_t)width * height;
+    TemporalPlanes T{};
+    T.a = a->rgb_a, T.b = a->rgb_b, T.hit_id = a->hit_id, T.position = a->position, T.normal = a->normal;
+    T.albedo = a->albedo, T.depth = a->depth;
+    if (a->hist_len) {
+        T.hist_a = a->hist_a, T.hist_b = a->hist_b, T.hist_len = a->hist_len, T.hist_hit_id = a->hist_hit_id;
+        T.hist_position = a->hist_position, T.hist_normal = a->hist_normal;
+        T.cam = temporal_cam(*a->prev_cam);
+    }
+    T.npix = n, T.W = width, T.H = height;
+    T.max_history = (double)a->max_history, T.normal_max = a->normal_max, T.plane_max = a->plane_max;
+    T.demod = demod ? 1 : 0;
+    for (int32_t y = 0; y < height; ++y)
+        for (int32_t x = 0; x < width; ++x) {
+            const TemporalPixel r = temporal_pixel(T, x, y);
+            const int64_t ip = (int64_t)y * width + x;
+            a->out_a[ip] = r.a.x; a->out_a[n + ip] = r.a.y; a->out_a[2 * n + ip] = r.a.z;
+            a->out_b[ip] = r.b.x; a->out_b[n + ip] = r.b.y; a->out_b[2 * n + ip] = r.b.z;
+            a->out_hist_a[ip] = r.hist_a.x; a->out_hist_a[n + ip] = r.hist_a.y; a->out_hist_a[2 * n + ip] = r.hist_a.z;
+            a->out_hist_b[ip] = r.hist_b.x; a->out_hist_b[n + ip] = r.hist_b.y; a->out_hist_b[2 * n + ip] = r.hist_b.z;
+            a->out_len[ip] = r.len;
+        }
+    if (a->ms_kernel) *a->ms_kernel = 0.0;
+    return SRT_OK;
+}
+
 // rt_device.h's Philox4x32-10 and path hash (known-answer tests of the Monte-Carlo stream)
 void hc_philox(const uint32_t* ctr, uint32_t k0, uint32_t k1, uint32_t* out) {
     const u4 r = philox(u4{ctr[0], ctr[1], ctr[2], ctr[3]}, k0, k1);

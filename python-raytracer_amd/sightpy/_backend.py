@@ -557,23 +557,33 @@ def denoise_params(spec):
     """Scene.render's `denoise` argument -> the filter's parameters (N.DENOISE_DEFAULTS overridden by a
     dict), or None for no denoising.  ValueError for an unknown key or a value srt_denoise would refuse.
     With "variance" or "demodulate" on, the dict also holds N.DENOISE_VAR_DEFAULTS' keys (the half-frame mode,
-    srt_denoise_var); otherwise it holds srt_denoise's parameters alone."""
+    srt_denoise_var); otherwise it holds srt_denoise's parameters alone.  With "temporal" on (which selects the
+    half-frame mode too) it also holds N.TEMPORAL_DEFAULTS' keys (srt_temporal_accumulate)."""
     if spec is None or spec is False:
         return None
     params = dict(N.DENOISE_DEFAULTS)
     if spec is True:
         return params
-    known = sorted(list(params) + list(N.DENOISE_VAR_DEFAULTS))
+    known = sorted(list(params) + list(N.DENOISE_VAR_DEFAULTS) + list(N.TEMPORAL_DEFAULTS))
     if not isinstance(spec, dict):
         raise ValueError("denoise must be a bool or a dict of %s" % known)
     extra = dict(N.DENOISE_VAR_DEFAULTS)
+    temporal = dict(N.TEMPORAL_DEFAULTS)
     for k, v in spec.items():
-        if k not in params and k not in extra:
+        if k not in params and k not in extra and k not in temporal:
             raise ValueError("denoise: unknown key %r (known: %s)" % (k, ", ".join(known)))
-        if k in ("variance", "demodulate"):
+        if k in ("variance", "demodulate", "temporal"):
             if not isinstance(v, (bool, np.bool_)):
                 raise ValueError("denoise: %s must be a bool, not %r" % (k, v))
-            extra[k] = bool(v)
+            (temporal if k == "temporal" else extra)[k] = bool(v)
+        elif k == "max_history":
+            if isinstance(v, bool) or int(v) != v or not 1 <= int(v) <= 2**31 - 1:
+                raise ValueError("denoise: max_history must be an integer >= 1, not %r" % (v,))
+            temporal[k] = int(v)
+        elif k in ("temporal_normal", "temporal_plane"):
+            if isinstance(v, bool) or not float(v) >= 0.0 or float(v) == float("inf"):
+                raise ValueError("denoise: %s must be a finite number >= 0, not %r" % (k, v))
+            temporal[k] = float(v)
         elif k == "sigma_lum":
             if isinstance(v, bool) or not float(v) > 0.0 or float(v) == float("inf"):
                 raise ValueError("denoise: %s must be a positive number, not %r" % (k, v))
@@ -586,8 +596,10 @@ def denoise_params(spec):
             if isinstance(v, bool) or not float(v) > 0.0 or float(v) == float("inf"):
                 raise ValueError("denoise: %s must be a positive number, not %r" % (k, v))
             params[k] = float(v)
-    if extra["variance"] or extra["demodulate"]:
+    if extra["variance"] or extra["demodulate"] or temporal["temporal"]:
         params.update(extra)
+    if temporal["temporal"]:
+        params.update(temporal)
     return params
 
 
@@ -656,13 +668,16 @@ def denoise(rgb, aovs, width, height, levels=N.DENOISE_DEFAULTS["levels"],
     return out, (None if u8 is None else u8.reshape(H, W, ch))
 
 
-def render_aovs_device(scene, pool):
+def render_aovs_device(scene, pool, hit_id=False):
     """render_aovs' normal, albedo, position and depth images left in device memory of `pool` (a DeviceArrays):
-    {"normal", "albedo", "position", "depth": device pointers, "ms_kernel"}."""
+    {"normal", "albedo", "position", "depth": device pointers, "ms_kernel"}; with `hit_id` also "hit_id", the
+    int32 plane."""
     upload(scene, ctx=pool.ctx)
     cd = camera_desc(scene.camera)
     n = int(scene.camera.screen_width) * int(scene.camera.screen_height)
     res = {k: pool.doubles(rows * n) for k, rows in (("normal", 3), ("albedo", 3), ("position", 3), ("depth", 1))}
+    if hit_id:
+        res["hit_id"] = pool.alloc(4 * n)
     out = N.AovOut()
     for k, p in res.items():
         setattr(out, k, p.value)
@@ -784,6 +799,131 @@ def denoise_var(rgb_a, rgb_b, spp_a, spp_b, aovs, width, height, variance=False,
     if timings is not None:
         timings.extend(float(v) for v in ms)
     return out, var, (None if u8 is None else u8.reshape(H, W, ch))
+
+
+def temporal_accumulate(rgb_a, rgb_b, aovs, width, height, history=None, prev_cam=None, demodulate=False,
+                        max_history=N.TEMPORAL_DEFAULTS["max_history"], normal_max=N.TEMPORAL_DEFAULTS["temporal_normal"],
+                        plane_max=N.TEMPORAL_DEFAULTS["temporal_plane"], out=None, timings=None, ctx=None):
+    """srt_temporal_accumulate: the half-frames `rgb_a`, `rgb_b` of the current frame blended with the reprojected
+    history of the earlier frames, each half with its own.  `aovs`: the current guides ("hit_id" int32, "position",
+    "normal", "depth", and "albedo" with `demodulate`).  `history`: None for a first frame, else the previous
+    call's {"a", "b", "len"} (its "hist_a", "hist_b", "len" results) with that frame's guides {"hit_id", "position",
+    "normal"}, and `prev_cam` that frame's CameraDesc (xs / ys are not read).  Arrays are numpy arrays or device
+    pointers (ctypes.c_void_p / int: used in place).  `out`: None for new host arrays, else the device pointers
+    {"a", "b", "hist_a", "hist_b", "len"} to write ("a" / "b" may be `rgb_a` / `rgb_b`; "hist_*" / "len" must not
+    be the history's).  Returns {"a", "b", "hist_a", "hist_b" (3, n), "len" (n,)}, or `out` itself.
+    `timings` receives the kernel's time, ms by HIP events."""
+    lib = library()
+    if ctx is None:
+        ctx = context()[1]
+    W, H = int(width), int(height)
+    n = W * H
+    a = N.TemporalArgs()
+    keep = []
+
+    def put(field, v, rows, dtype=np.float64):
+        if isinstance(v, (ctypes.c_void_p, int)):
+            setattr(a, field, _addr(v))
+            return
+        v = np.ascontiguousarray(v, dtype=dtype)
+        if v.size != rows * n:
+            raise ValueError("temporal_accumulate: %s must hold %d x %d values" % (field, rows, n))
+        keep.append(v)
+        setattr(a, field, N.ptr(v))
+
+    put("rgb_a", rgb_a, 3)
+    put("rgb_b", rgb_b, 3)
+    put("hit_id", aovs["hit_id"], 1, np.int32)
+    for k, rows in (("position", 3), ("normal", 3), ("depth", 1)):
+        put(k, aovs[k], rows)
+    if demodulate:
+        put("albedo", aovs["albedo"], 3)
+    if history is not None:
+        if prev_cam is None:
+            raise ValueError("temporal_accumulate: a history needs the camera of its frame (prev_cam)")
+        put("hist_a", history["a"], 3)
+        put("hist_b", history["b"], 3)
+        put("hist_len", history["len"], 1)
+        put("hist_hit_id", history["hit_id"], 1, np.int32)
+        put("hist_position", history["position"], 3)
+        put("hist_normal", history["normal"], 3)
+        a.prev_cam = ctypes.pointer(prev_cam)
+    a.max_history = int(max_history)
+    a.flags = N.TEMPORAL_DEMODULATE if demodulate else 0
+    a.normal_max, a.plane_max = float(normal_max), float(plane_max)
+    fields = (("a", "out_a", 3), ("b", "out_b", 3), ("hist_a", "out_hist_a", 3), ("hist_b", "out_hist_b", 3),
+              ("len", "out_len", 1))
+    if out is None:
+        res = {k: np.empty((3, n) if rows == 3 else n) for k, _, rows in fields}
+        for k, field, _ in fields:
+            setattr(a, field, N.ptr(res[k]))
+    else:
+        res = out
+        for k, field, _ in fields:
+            setattr(a, field, _addr(out[k]))
+    ms = ctypes.c_double(0.0)
+    a.ms_kernel = ctypes.pointer(ms)
+    N.check(lib, lib.srt_temporal_accumulate(ctx, W, H, ctypes.byref(a)))
+    if timings is not None:
+        timings.append(float(ms.value))
+    return res
+
+
+class TemporalHistory:
+    """What srt_temporal_accumulate carries from one frame of a sequence to the next, in device memory of the
+    process context (device_buffer / release_buffer): two sets of the accumulated half-frames and their lengths
+    ("a", "b" (3, n), "len" (n,)) and of the frame's guides ("hit_id" int32, "position", "normal"), swapped every
+    frame -- the call reads one set and writes the other -- and the previous frame's camera.  reset(), and a
+    frame of another size, drop everything."""
+
+    PLANES = (("a", 24), ("b", 24), ("len", 8), ("hit_id", 4), ("position", 24), ("normal", 24))  # bytes per pixel
+
+    def __init__(self):
+        self.size = None      # (W, H) of the buffers
+        self.cur = 0          # the set holding the previous frame
+        self.prev_cam = None  # that frame's CameraDesc; None: no history
+
+    def _name(self, k, s):
+        return "temporal_%x_%s%d" % (id(self), k, s)
+
+    def reset(self):
+        if self.size is not None:
+            for s in (0, 1):
+                for k, _ in self.PLANES:
+                    release_buffer(self._name(k, s))
+        self.size, self.prev_cam, self.cur = None, None, 0
+
+    def _set(self, s, n):
+        return {k: device_buffer(self._name(k, s), bytes_pp * n) for k, bytes_pp in self.PLANES}
+
+    def accumulate(self, rgb_a, rgb_b, aovs, cam_desc, width, height, demodulate=False, timings=None, **params):
+        """One frame: the device half-frames `rgb_a`, `rgb_b` are accumulated in place against the history, which
+        then becomes this frame's (`aovs`: device guides with "hit_id"; `cam_desc`: the frame's CameraDesc;
+        `params`: temporal_accumulate's max_history / normal_max / plane_max)."""
+        lib, ctx = context()
+        W, H = int(width), int(height)
+        n = W * H
+        if self.size != (W, H):
+            self.reset()
+            self.size = (W, H)
+        prev, nxt = self._set(self.cur, n), self._set(1 - self.cur, n)
+        temporal_accumulate(rgb_a, rgb_b, aovs, W, H, history=prev if self.prev_cam is not None else None,
+                            prev_cam=self.prev_cam, demodulate=demodulate, timings=timings,
+                            out={"a": rgb_a, "b": rgb_b, "hist_a": nxt["a"], "hist_b": nxt["b"], "len": nxt["len"]},
+                            **params)
+        for k, bytes_pp in self.PLANES[3:]:  # this frame's guides are the next frame's history guides
+            N.check(lib, lib.srt_memcpy(ctx, nxt[k], _addr(aovs[k]), bytes_pp * n))
+        cam = N.CameraDesc()
+        ctypes.memmove(ctypes.byref(cam), ctypes.byref(cam_desc), ctypes.sizeof(cam))
+        cam.xs = cam.ys = None
+        self.prev_cam, self.cur = cam, 1 - self.cur
+
+    def __del__(self):
+        try:
+            if _STATE["ctx"] is not None:
+                self.reset()
+        except Exception:  # (interpreter shutdown: the process frees it)
+            pass
 
 
 def primary_rays(camera, jitter):

@@ -303,6 +303,41 @@ class DenoiseVarArgs(ctypes.Structure):
     ]
 
 
+class TemporalArgs(ctypes.Structure):
+    """srt_temporal_args."""
+    _fields_ = [
+        ("rgb_a", _p),
+        ("rgb_b", _p),
+        ("hit_id", _p),
+        ("position", _p),
+        ("normal", _p),
+        ("albedo", _p),
+        ("depth", _p),
+        ("prev_cam", ctypes.POINTER(CameraDesc)),
+        ("hist_a", _p),
+        ("hist_b", _p),
+        ("hist_len", _p),
+        ("hist_hit_id", _p),
+        ("hist_position", _p),
+        ("hist_normal", _p),
+        ("max_history", ctypes.c_int32),
+        ("flags", ctypes.c_int32),
+        ("normal_max", ctypes.c_double),
+        ("plane_max", ctypes.c_double),
+        ("out_a", _p),
+        ("out_b", _p),
+        ("out_hist_a", _p),
+        ("out_hist_b", _p),
+        ("out_len", _p),
+        ("ms_kernel", ctypes.POINTER(ctypes.c_double)),
+    ]
+
+
+TEMPORAL_DEMODULATE = 1  # SRT_TEMPORAL_DEMODULATE
+# what Scene.render(denoise={...}) takes for the temporal pass of srt_temporal_accumulate ("temporal": True selects
+# the half-frame mode as `variance` / `demodulate` do); untuned beyond the 64 x 64 cornell fixture
+TEMPORAL_DEFAULTS = {"temporal": False, "max_history": 32, "temporal_normal": 0.1, "temporal_plane": 0.02}
+
 DENOISE_RGBX, DENOISE_VARIANCE, DENOISE_DEMODULATE = 2, 4, 8  # SRT_DENOISE_*
 DENOISE_MAX_LEVELS = 8
 # srt_denoise's defaults (Scene.render(denoise=True)); untuned beyond 64-128 px cornell frames
@@ -338,6 +373,7 @@ SIGNATURES = {
     "srt_render_aovs": (ctypes.c_int, [_p, ctypes.POINTER(CameraDesc), ctypes.POINTER(AovOut)]),
     "srt_denoise": (ctypes.c_int, [_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(DenoiseArgs)]),
     "srt_denoise_var": (ctypes.c_int, [_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(DenoiseVarArgs)]),
+    "srt_temporal_accumulate": (ctypes.c_int, [_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(TemporalArgs)]),
     "srt_mt19937_uniforms": (ctypes.c_int, [_p, _p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, _p, _p,
                                             ctypes.POINTER(ctypes.c_int32)]),
     "srt_device_alloc": (ctypes.c_int, [_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p)]),

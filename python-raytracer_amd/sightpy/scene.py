@@ -31,6 +31,7 @@ class Scene:
         self.ambient_color = ambient_color
         self.n = n
         self.last_stats = None
+        self._history = None  # _backend.TemporalHistory of render(denoise={"temporal": True})
 
     def add_Camera(self, look_from, look_at, **kwargs):
         self.camera = Camera(look_from, look_at, **kwargs)
@@ -103,6 +104,16 @@ class Scene:
         `demodulate` filters colour / albedo and multiplies the albedo back, which keeps texture detail.
         Half-frames, guides and the filter's planes stay in device memory; only the uint8 image is copied
         out.  Needs spp >= 2 (ValueError) and a single GPU (NotImplementedError with several selected).
+
+        `"temporal": True` (off by default; it selects the half-frame mode too, and `variance` / `demodulate` keep
+        their meaning) is for the frames of an animation: before the filter runs, each half-frame is blended with
+        its own history -- the accumulated half-frames of the earlier frames of this scene, reprojected through the
+        previous frame's camera and accepted where collider id, normal and plane distance agree
+        (srt_temporal_accumulate; `"max_history"`, default 32, bounds the accumulated length, `"temporal_normal"`
+        0.1 and `"temporal_plane"` 0.02 are the two acceptance thresholds).  With `demodulate` the history holds
+        colour / albedo.  The history lives in device memory with the scene; `reset_history()` drops it, as does
+        a frame of another size.  Moving objects are reprojected as if static (their history is rejected where
+        the geometry changed).
         """
         from . import _backend as B
         from . import _hybrid
@@ -190,38 +201,56 @@ class Scene:
         return B.rgb_image(u8, W, H, mapped=blk is not None)
 
     def _render_denoised_halves(self, samples_per_pixel, batch_size, rng, seed, params):
-        """render(denoise={"variance" / "demodulate": True, ...}): the frame as two half-frames
-        (_backend.render_halves), the guide images and srt_denoise_var, all in device memory of the context;
-        the image is the filter's own resolve into the pinned image block."""
+        """render(denoise={"variance" / "demodulate" / "temporal": True, ...}): the frame as two half-frames
+        (_backend.render_halves), the guide images, with `temporal` srt_temporal_accumulate against the scene's
+        history, and srt_denoise_var, all in device memory of the context; the image is the filter's own resolve
+        into the pinned image block."""
         from . import _backend as B
         from . import _hybrid
 
         if rng not in ("numpy", "numpy-host", "device"):
             raise ValueError("rng must be 'numpy', 'numpy-host' or 'device'")
         if int(samples_per_pixel) < 2:
-            raise ValueError("denoise: variance / demodulate split the frame into two half-frames and need "
+            raise ValueError("denoise: variance / demodulate / temporal split the frame into two half-frames and need "
                              "samples_per_pixel >= 2, not %r" % (samples_per_pixel,))
         if _hybrid.is_hybrid(self):
             raise NotImplementedError("denoise: a scene with user Collider / Material / texture / Light subclasses "
                                       "is shaded through the host; its guide images are not computed on the device")
         if len(B.devices()) > 1:
-            raise NotImplementedError("denoise: variance / demodulate render on one GPU; %d are selected "
+            raise NotImplementedError("denoise: variance / demodulate / temporal render on one GPU; %d are selected "
                                       "($SIGHTPY_DEVICES)" % len(B.devices()))
         print("Rendering...")
         t0 = time.time()
         H, W = int(self.camera.screen_height), int(self.camera.screen_width)
+        temporal = params.get("temporal", False)
+        filt = {k: v for k, v in params.items() if k not in B.N.TEMPORAL_DEFAULTS}
+        extra = {}
         with B.DeviceArrays() as pool:
             A, Bh, ka, kb, stats = B.render_halves(self, samples_per_pixel, rng=rng, seed=seed, batch_size=batch_size,
                                                    pool=pool)
-            aovs = B.render_aovs_device(self, pool)
+            aovs = B.render_aovs_device(self, pool, hit_id=temporal)
+            if temporal:
+                # the half-frames are accumulated in place against this scene's history before the filter sees them
+                if self._history is None:
+                    self._history = B.TemporalHistory()
+                mt = []
+                self._history.accumulate(A, Bh, aovs, B.camera_desc(self.camera), W, H, demodulate=params["demodulate"],
+                                         timings=mt, max_history=params["max_history"],
+                                         normal_max=params["temporal_normal"], plane_max=params["temporal_plane"])
+                extra["ms_temporal"] = mt[0]
             blk = B.image_block(4 * W * H)
             ms = []
             _, _, u8 = B.denoise_var(A, Bh, ka, kb, aovs, W, H, want_rgb=False, rgbx=True, out_u8=blk, timings=ms,
-                                     **params)
+                                     **filt)
         self.last_stats = dict(stats, denoise=dict(params, ka=ka, kb=kb, ms_aov_kernel=aovs["ms_kernel"],
-                                                   ms_levels=ms[:-2], ms_filter=ms[-2], ms_prepare=ms[-1]))
+                                                   ms_levels=ms[:-2], ms_filter=ms[-2], ms_prepare=ms[-1], **extra))
         print("Render Took", time.time() - t0)
         return B.rgb_image(u8, W, H, mapped=blk is not None)
+
+    def reset_history(self):
+        """Drop the temporal history of render(denoise={"temporal": True}): the next such frame starts anew."""
+        if self._history is not None:
+            self._history.reset()
 
     def get_aovs(self):
         """The first-hit guide images a denoiser needs (no reference counterpart), computed on the GPU

@@ -3,7 +3,8 @@
     python tools/resource_usage.py [--filter k_primary] [--source csrc/rt_kernels.hip] [--define X ...]
 
 Runs `hipcc -Rpass-analysis=kernel-resource-usage` (the Makefile's `resource-usage` flags) on the
-kernel source and prints one line per kernel: VGPRs, VGPR spill, scratch bytes/lane, LDS bytes/block, waves/SIMD.
+kernel source and prints one line per kernel: VGPRs, VGPR spill, scratch bytes/lane, LDS bytes/block, waves/SIMD,
+SGPRs, SGPR spill.
 """
 import argparse
 import re
@@ -50,12 +51,13 @@ def main():
     a = ap.parse_args()
     rows = usage(a.source, a.define)
     pat = re.compile(a.filter)
-    print("%-60s %6s %6s %8s %6s %5s" % ("kernel", "VGPRs", "spill", "scratch", "LDS", "occ"))
+    print("%-60s %6s %6s %8s %6s %5s %6s %7s" % ("kernel", "VGPRs", "spill", "scratch", "LDS", "occ", "SGPRs", "s-spill"))
     for r in rows:
         if pat.search(r["pretty"]):
-            print("%-60s %6s %6s %8s %6s %5s" % (r["pretty"][:60], r.get("VGPRs"), r.get("VGPRs Spill"),
-                                               r.get("ScratchSize [bytes/lane]"), r.get("LDS Size [bytes/block]"),
-                                               r.get("Occupancy [waves/SIMD]")))
+            print("%-60s %6s %6s %8s %6s %5s %6s %7s" % (r["pretty"][:60], r.get("VGPRs"), r.get("VGPRs Spill"),
+                                                       r.get("ScratchSize [bytes/lane]"), r.get("LDS Size [bytes/block]"),
+                                                       r.get("Occupancy [waves/SIMD]"), r.get("TotalSGPRs"),
+                                                       r.get("SGPRs Spill")))
     return 0
 
 
