@@ -572,10 +572,22 @@ int srt_denoise_var(srt_ctx* ctx, int32_t width, int32_t height, const srt_denoi
  * hist_normal, with out_hist_a / out_hist_b / out_len and the current camera.  Pointers may address host or
  * device memory (device arrays are used and written in place); out_a / out_b may be rgb_a / rgb_b themselves,
  * the out_hist_* arrays must not be the hist_* arrays.  Needs no scene.
+ * motion != NULL (with a history; a first frame ignores it): per-collider motion.  motion[n_motion][12], host or
+ * device memory; row m belongs to the collider with device index m (the hit_id of srt_render_aovs), entries 0..8
+ * a 3x3 matrix R, row-major, entries 9..11 a vector t: together they map a point on that collider in the current
+ * frame to the same surface point in the previous frame.  With id = hit_id_p:
+ *   id < 0 or id >= n_motion: no history
+ *   x'_k = ((R[k][0] * x_p.x + R[k][1] * x_p.y) + R[k][2] * x_p.z) + t[k]
+ *   n'_k = (R[k][0] * n_p.x + R[k][1] * n_p.y) + R[k][2] * n_p.z
+ *   e = x' - look_from', and a tap counts with n' for n_p and x' for x_p: |n' - n_q|^2 <= normal_max and
+ *   |n' . (x_q - x')| / t_p <= plane_max (t_p unchanged); everything else as above
+ * A row holding a NaN leaves its collider's pixels without history (out_a = A, out_b = B bit for bit, out_len = 1):
+ * the way to say that a collider changed otherwise than by a rigid motion.  Rows are expected to be rigid; that
+ * is not checked, and n' is not renormalised.  motion == NULL: the results above, bit for bit; n_motion is not read.
  * SRT_ERR_ARG: a non-positive size, max_history < 1, a negative or non-finite normal_max / plane_max, an unknown
  * flag, a NULL rgb_a / rgb_b / hit_id / position / normal / depth or output, a NULL albedo with DEMODULATE,
  * hist_len given with another hist_* pointer or prev_cam NULL, prev_cam of another width or height, out_hist_a/b
- * / out_len equal to hist_a/b / hist_len. */
+ * / out_len equal to hist_a/b / hist_len, motion given with n_motion < 1. */
 #define SRT_TEMPORAL_DEMODULATE 1 /* accumulate colour / max(albedo, 1e-3); out_a / out_b are multiplied back */
 typedef struct srt_temporal_args {
     const double* rgb_a;         /* [3][n] half-frame A of the current frame, linear RGB */
@@ -602,6 +614,8 @@ typedef struct srt_temporal_args {
     double* out_hist_b;          /* [3][n] */
     double* out_len;             /* [n]    the next call's hist_len */
     double* ms_kernel;           /* host: duration of the kernel (HIP events), or NULL */
+    const double* motion;        /* [n_motion][12] per-collider rows (R row-major, then t), or NULL: no motion */
+    int32_t n_motion;            /* >= 1 with motion; not read without */
 } srt_temporal_args;
 int srt_temporal_accumulate(srt_ctx* ctx, int32_t width, int32_t height, const srt_temporal_args* args);
 /* numpy's legacy global-RNG stream on the device: writes the n_out doubles that

@@ -453,6 +453,7 @@ int srt_temporal_accumulate(srt_ctx* c, int32_t width, int32_t height, const srt
         if (a->out_hist_a == a->hist_a || a->out_hist_b == a->hist_b || a->out_len == a->hist_len)
             return fail(SRT_ERR_ARG, "srt_temporal_accumulate: the history cannot be updated in place");
     }
+    if (a->motion && a->n_motion < 1) return fail(SRT_ERR_ARG, "srt_temporal_accumulate: motion with n_motion < 1");
     HIP_TRY(hipSetDevice(c->device));
     DevList bufs;
     const int64_t n = (int64_t)width * height;
@@ -477,6 +478,11 @@ int srt_temporal_accumulate(srt_ctx* c, int32_t width, int32_t height, const srt
         HIP_TRY(stage_in(bufs, a->hist_position, 3 * n, &T.hist_position));
         HIP_TRY(stage_in(bufs, a->hist_normal, 3 * n, &T.hist_normal));
     }
+    const bool motion = a->motion && a->hist_len;  // a first frame ignores the table
+    if (motion) {
+        T.n_motion = a->n_motion;
+        HIP_TRY(stage_in(bufs, a->motion, (int64_t)a->n_motion * 12, &T.motion));
+    }
     // an output in device memory is written in place, a host array through a buffer of the call
     double* const host[5] = {a->out_a, a->out_b, a->out_hist_a, a->out_hist_b, a->out_len};
     const int64_t count[5] = {3 * n, 3 * n, 3 * n, 3 * n, n};
@@ -495,7 +501,10 @@ int srt_temporal_accumulate(srt_ctx* c, int32_t width, int32_t height, const srt
     const int64_t items = (((int64_t)width + 63) / 64) * height, blocks = (items + DN_BLOCK / 64 - 1) / (DN_BLOCK / 64);
     if (blocks > 0x7fffffff) return fail(SRT_ERR_ARG, "srt_temporal_accumulate: image too large");
     HIP_TRY(hipEventRecord(ev.e[0], st));
-    hipLaunchKernelGGL(k_temporal, dim3((unsigned)blocks), dim3(DN_BLOCK), 0, st, T, out);
+    if (motion)
+        hipLaunchKernelGGL(k_temporal<true>, dim3((unsigned)blocks), dim3(DN_BLOCK), 0, st, T, out);
+    else
+        hipLaunchKernelGGL(k_temporal<false>, dim3((unsigned)blocks), dim3(DN_BLOCK), 0, st, T, out);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev.e[1], st));
     HIP_TRY(hipStreamSynchronize(st));

@@ -76,6 +76,23 @@
 //     out_len = N, out_hist_a/b = uA'/uB', out_a/b = uA' * d / uB' * d (uA' / uB' themselves without DEMODULATE)
 //   without (a disocclusion included): out_a = A, out_b = B (bit for bit), out_hist_a/b = uA/uB, out_len = 1
 // The current frame's hit_id / position / normal are the next call's history guides; the caller keeps them.
+//
+// Per-collider motion (motion != NULL; k_temporal<true>, tests/temporal_motion_ref.py restates it).  motion[n_motion][12],
+// float64: row m belongs to the collider whose device index is m (the hit_id srt_render_aovs writes); entries 0..8
+// are a 3x3 matrix R, row-major, entries 9..11 a vector t, and together they map a point on that collider in the
+// current frame to the same surface point in the previous frame.  For an ok pixel with history present, id = hit_id_p:
+//   id < 0 or id >= n_motion: no history (the "without" branch above)
+//   x'_k = ((R[k][0] * x_p.x + R[k][1] * x_p.y) + R[k][2] * x_p.z) + t[k]
+//   n'_k = (R[k][0] * n_p.x + R[k][1] * n_p.y) + R[k][2] * n_p.z
+//   the projection takes e = x' - look_from'; a tap is valid under the conditions above with n' in place of n_p
+//   and x' in place of x_p: |n' - n_q|^2 <= normal_max and |dot(n', x_q - x')| / t_p <= plane_max (t_p is the
+//   current depth, unchanged); everything after the taps is unchanged
+// which is the definition above on guides whose position and normal are x' and n' (depth, hit_id and albedo as they
+// are).  A row holding a NaN gives a NaN zc, which fails zc > 0: that collider's pixels take the "without" branch
+// (out_a = A, out_b = B bit for bit, out_len = 1) -- how a caller says "this collider changed in a way a rigid
+// transform does not express".  Rows are expected to be rigid; nothing checks it and n' is not renormalised.  The
+// identity row (1,0,0, 0,1,0, 0,0,1, 0,0,0) gives x' = x_p and n' = n_p bit for bit (x*1 + y*0 + z*0 + 0 on finite
+// guides; the sign of a zero may differ, which no later step tells apart).
 #ifndef RT_DENOISE_H
 #define RT_DENOISE_H
 
@@ -299,6 +316,10 @@ struct TemporalPlanes {
     TemporalCam cam;
     double max_history, normal_max, plane_max;
     int32_t demod;
+    // [n_motion][12] rows (R row-major, t), read by temporal_pixel<true> alone: the <false> kernel never loads
+    // these two arguments, so they cost it no SGPR
+    int32_t n_motion;
+    const double* motion;
 };
 
 struct TemporalPixel {
@@ -308,6 +329,8 @@ struct TemporalPixel {
 
 RT_HD d3 tp_div3(d3 a, d3 d) { return d3{a.x / d.x, a.y / d.y, a.z / d.z}; }
 
+// MOTION: x_p and n_p go through the pixel's row of T.motion first (header comment)
+template <bool MOTION>
 RT_HD TemporalPixel temporal_pixel(const TemporalPlanes& T, int32_t x, int32_t y) {
     const int64_t n = T.npix, ip = (int64_t)y * T.W + x;
     const d3 A = dn_ld3(T.a, n, ip), B = dn_ld3(T.b, n, ip), nrm = dn_ld3(T.normal, n, ip);
@@ -324,7 +347,19 @@ RT_HD TemporalPixel temporal_pixel(const TemporalPlanes& T, int32_t x, int32_t y
     }
     r.len = 1.0;
     if (!T.hist_len) return r;
-    const d3 xp = dn_ld3(T.position, n, ip);
+    d3 xp = dn_ld3(T.position, n, ip);
+    d3 np = nrm;
+    int32_t id;
+    if constexpr (MOTION) {
+        id = T.hit_id[ip];
+        if (id < 0 || id >= T.n_motion) return r;
+        const double* M = T.motion + (int64_t)id * 12;
+        const d3 x0 = xp;
+        xp = d3{((M[0] * x0.x + M[1] * x0.y) + M[2] * x0.z) + M[9], ((M[3] * x0.x + M[4] * x0.y) + M[5] * x0.z) + M[10],
+                ((M[6] * x0.x + M[7] * x0.y) + M[8] * x0.z) + M[11]};
+        np = d3{(M[0] * nrm.x + M[1] * nrm.y) + M[2] * nrm.z, (M[3] * nrm.x + M[4] * nrm.y) + M[5] * nrm.z,
+                (M[6] * nrm.x + M[7] * nrm.y) + M[8] * nrm.z};
+    }
     const d3 e = sub(xp, T.cam.from);
     const double zc = dot(e, T.cam.fwd);
     const double xc = dot(e, T.cam.right) / zc, yc = dot(e, T.cam.up) / zc;
@@ -334,7 +369,7 @@ RT_HD TemporalPixel temporal_pixel(const TemporalPlanes& T, int32_t x, int32_t y
     const double xf = floor(fx), yf = floor(fy);
     const double ax = fx - xf, ay = fy - yf;
     const int32_t x0 = (int32_t)xf, y0 = (int32_t)yf;
-    const int32_t id = T.hit_id[ip];
+    if constexpr (!MOTION) id = T.hit_id[ip];
     const double tp = T.depth[ip];
     const double wt[4] = {(1.0 - ax) * (1.0 - ay), ax * (1.0 - ay), (1.0 - ax) * ay, ax * ay};
     double sw = 0.0, L = 0.0;
@@ -346,8 +381,8 @@ RT_HD TemporalPixel temporal_pixel(const TemporalPlanes& T, int32_t x, int32_t y
         const int64_t q = (int64_t)qy * T.W + qx;
         const double lq = T.hist_len[q];
         if (!(lq >= 1.0) || T.hist_hit_id[q] != id) continue;
-        if (!(dn_sq(sub(nrm, dn_ld3(T.hist_normal, n, q))) <= T.normal_max)) continue;
-        if (!(fabs(dot(nrm, sub(dn_ld3(T.hist_position, n, q), xp))) / tp <= T.plane_max)) continue;
+        if (!(dn_sq(sub(np, dn_ld3(T.hist_normal, n, q))) <= T.normal_max)) continue;
+        if (!(fabs(dot(np, sub(dn_ld3(T.hist_position, n, q), xp))) / tp <= T.plane_max)) continue;
         sw += w;
         hA = add(hA, mul(dn_ld3(T.hist_a, n, q), w));
         hB = add(hB, mul(dn_ld3(T.hist_b, n, q), w));
@@ -469,7 +504,10 @@ struct TemporalOut {
 // 18 plane pointers and the camera stay live across it and 88 SGPRs spill; without it none does
 // (profiles/temporal_resource_usage.txt).  No LDS, no atomics.  out.a / out.b may be the planes T.a / T.b
 // themselves (a pixel reads only its own A, B); the out.hist_* planes must not be the T.hist_* planes, which
-// other pixels gather from.
+// other pixels gather from.  MOTION: each lane also loads the 12 doubles of its collider's row of T.motion (ordinary
+// vector loads of a table of a few KB, which the caches hold) and spends 18 multiply-adds on x' and n'
+// (profiles/temporal_motion_resource_usage.txt).
+template <bool MOTION>
 __global__ __launch_bounds__(DN_BLOCK) void k_temporal(TemporalPlanes T, TemporalOut out) {
     const int64_t segs = (T.W + 63) / 64, items = segs * T.H;
     constexpr int WAVES = DN_BLOCK / 64;
@@ -479,7 +517,7 @@ __global__ __launch_bounds__(DN_BLOCK) void k_temporal(TemporalPlanes T, Tempora
     const int64_t x = (it - y * segs) * 64 + (threadIdx.x & 63);
     if (x >= T.W) return;
     const int64_t n = T.npix;
-    const TemporalPixel r = temporal_pixel(T, (int32_t)x, (int32_t)y);
+    const TemporalPixel r = temporal_pixel<MOTION>(T, (int32_t)x, (int32_t)y);
     const int64_t ip = y * T.W + x;
     out.a[ip] = r.a.x; out.a[n + ip] = r.a.y; out.a[2 * n + ip] = r.a.z;
     out.b[ip] = r.b.x; out.b[n + ip] = r.b.y; out.b[2 * n + ip] = r.b.z;

@@ -474,7 +474,8 @@ int hc_temporal(int32_t width, int32_t height, const srt_temporal_args* a) {
         !a->depth || (demod && !a->albedo) || !a->out_a || !a->out_b || !a->out_hist_a || !a->out_hist_b || !a->out_len ||
         (a->hist_len && (!a->hist_a || !a->hist_b || !a->hist_hit_id || !a->hist_position || !a->hist_normal ||
                          !a->prev_cam || a->prev_cam->width != width || a->prev_cam->height != height ||
-                         a->out_hist_a == a->hist_a || a->out_hist_b == a->hist_b || a->out_len == a->hist_len))) {
+                         a->out_hist_a == a->hist_a || a->out_hist_b == a->hist_b || a->out_len == a->hist_len)) ||
+        (a->motion && a->n_motion < 1)) {
         g_err = "hc_temporal: bad argument";
         return SRT_ERR_ARG;
     }
@@ -490,9 +491,11 @@ int hc_temporal(int32_t width, int32_t height, const srt_temporal_args* a) {
     T.npix = n, T.W = width, T.H = height;
     T.max_history = (double)a->max_history, T.normal_max = a->normal_max, T.plane_max = a->plane_max;
     T.demod = demod ? 1 : 0;
+    const bool motion = a->motion && a->hist_len;  // a first frame ignores the table
+    if (motion) T.motion = a->motion, T.n_motion = a->n_motion;
     for (int32_t y = 0; y < height; ++y)
         for (int32_t x = 0; x < width; ++x) {
-            const TemporalPixel r = temporal_pixel(T, x, y);
+            const TemporalPixel r = motion ? temporal_pixel<true>(T, x, y) : temporal_pixel<false>(T, x, y);
             const int64_t ip = (int64_t)y * width + x;
             a->out_a[ip] = r.a.x; a->out_a[n + ip] = r.a.y; a->out_a[2 * n + ip] = r.a.z;
             a->out_b[ip] = r.b.x; a->out_b[n + ip] = r.b.y; a->out_b[2 * n + ip] = r.b.z;

@@ -11,6 +11,7 @@ import numpy as np
 
 from . import _native as N
 from ._lower import lower_scene, camera_desc, collider_record
+from ._motion import collider_motion, count_rows
 from .utils.vector3 import vec3
 
 _STATE = {"lib": None, "ctx": None, "device": None, "scene_sig": {}, "scene_inputs": {}, "buffers": {}, "pinned": {}, "group": None}
@@ -558,24 +559,29 @@ def denoise_params(spec):
     dict), or None for no denoising.  ValueError for an unknown key or a value srt_denoise would refuse.
     With "variance" or "demodulate" on, the dict also holds N.DENOISE_VAR_DEFAULTS' keys (the half-frame mode,
     srt_denoise_var); otherwise it holds srt_denoise's parameters alone.  With "temporal" on (which selects the
-    half-frame mode too) it also holds N.TEMPORAL_DEFAULTS' keys (srt_temporal_accumulate)."""
+    half-frame mode too) it also holds N.TEMPORAL_DEFAULTS' keys (srt_temporal_accumulate), and "motion": True when
+    that key is given as True (per-collider motion, _motion.py; absent otherwise)."""
     if spec is None or spec is False:
         return None
     params = dict(N.DENOISE_DEFAULTS)
     if spec is True:
         return params
-    known = sorted(list(params) + list(N.DENOISE_VAR_DEFAULTS) + list(N.TEMPORAL_DEFAULTS))
+    known = sorted(list(params) + list(N.DENOISE_VAR_DEFAULTS) + list(N.TEMPORAL_DEFAULTS) + ["motion"])
     if not isinstance(spec, dict):
         raise ValueError("denoise must be a bool or a dict of %s" % known)
     extra = dict(N.DENOISE_VAR_DEFAULTS)
     temporal = dict(N.TEMPORAL_DEFAULTS)
+    motion = False
     for k, v in spec.items():
-        if k not in params and k not in extra and k not in temporal:
+        if k not in params and k not in extra and k not in temporal and k != "motion":
             raise ValueError("denoise: unknown key %r (known: %s)" % (k, ", ".join(known)))
-        if k in ("variance", "demodulate", "temporal"):
+        if k in ("variance", "demodulate", "temporal", "motion"):
             if not isinstance(v, (bool, np.bool_)):
                 raise ValueError("denoise: %s must be a bool, not %r" % (k, v))
-            (temporal if k == "temporal" else extra)[k] = bool(v)
+            if k == "motion":
+                motion = bool(v)
+            else:
+                (temporal if k == "temporal" else extra)[k] = bool(v)
         elif k == "max_history":
             if isinstance(v, bool) or int(v) != v or not 1 <= int(v) <= 2**31 - 1:
                 raise ValueError("denoise: max_history must be an integer >= 1, not %r" % (v,))
@@ -600,6 +606,8 @@ def denoise_params(spec):
         params.update(extra)
     if temporal["temporal"]:
         params.update(temporal)
+        if motion:
+            params["motion"] = True
     return params
 
 
@@ -671,8 +679,8 @@ def denoise(rgb, aovs, width, height, levels=N.DENOISE_DEFAULTS["levels"],
 def render_aovs_device(scene, pool, hit_id=False):
     """render_aovs' normal, albedo, position and depth images left in device memory of `pool` (a DeviceArrays):
     {"normal", "albedo", "position", "depth": device pointers, "ms_kernel"}; with `hit_id` also "hit_id", the
-    int32 plane."""
-    upload(scene, ctx=pool.ctx)
+    int32 plane, and "colliders", the lowered collider table (host, N.COLLIDER_DTYPE) whose indices it holds."""
+    L = upload(scene, ctx=pool.ctx)
     cd = camera_desc(scene.camera)
     n = int(scene.camera.screen_width) * int(scene.camera.screen_height)
     res = {k: pool.doubles(rows * n) for k, rows in (("normal", 3), ("albedo", 3), ("position", 3), ("depth", 1))}
@@ -683,6 +691,8 @@ def render_aovs_device(scene, pool, hit_id=False):
         setattr(out, k, p.value)
     N.check(pool.lib, pool.lib.srt_render_aovs(pool.ctx, ctypes.byref(cd), ctypes.byref(out)))
     res["ms_kernel"] = float(out.ms_kernel)
+    if hit_id:
+        res["colliders"] = L.colliders
     return res
 
 
@@ -803,7 +813,7 @@ def denoise_var(rgb_a, rgb_b, spp_a, spp_b, aovs, width, height, variance=False,
 
 def temporal_accumulate(rgb_a, rgb_b, aovs, width, height, history=None, prev_cam=None, demodulate=False,
                         max_history=N.TEMPORAL_DEFAULTS["max_history"], normal_max=N.TEMPORAL_DEFAULTS["temporal_normal"],
-                        plane_max=N.TEMPORAL_DEFAULTS["temporal_plane"], out=None, timings=None, ctx=None):
+                        plane_max=N.TEMPORAL_DEFAULTS["temporal_plane"], out=None, timings=None, ctx=None, motion=None):
     """srt_temporal_accumulate: the half-frames `rgb_a`, `rgb_b` of the current frame blended with the reprojected
     history of the earlier frames, each half with its own.  `aovs`: the current guides ("hit_id" int32, "position",
     "normal", "depth", and "albedo" with `demodulate`).  `history`: None for a first frame, else the previous
@@ -812,6 +822,8 @@ def temporal_accumulate(rgb_a, rgb_b, aovs, width, height, history=None, prev_ca
     pointers (ctypes.c_void_p / int: used in place).  `out`: None for new host arrays, else the device pointers
     {"a", "b", "hist_a", "hist_b", "len"} to write ("a" / "b" may be `rgb_a` / `rgb_b`; "hist_*" / "len" must not
     be the history's).  Returns {"a", "b", "hist_a", "hist_b" (3, n), "len" (n,)}, or `out` itself.
+    `motion`: None, or the per-collider table (rows, 12) that maps a current point of collider hit_id to its place
+    in the previous frame (_motion.collider_motion) -- a numpy array, or (device pointer, rows).
     `timings` receives the kernel's time, ms by HIP events."""
     lib = library()
     if ctx is None:
@@ -848,6 +860,15 @@ def temporal_accumulate(rgb_a, rgb_b, aovs, width, height, history=None, prev_ca
         put("hist_position", history["position"], 3)
         put("hist_normal", history["normal"], 3)
         a.prev_cam = ctypes.pointer(prev_cam)
+    if motion is not None:
+        if isinstance(motion, tuple):
+            a.motion, a.n_motion = _addr(motion[0]), int(motion[1])
+        else:
+            motion = np.ascontiguousarray(motion, dtype=np.float64)
+            if motion.ndim != 2 or motion.shape[1] != 12 or not len(motion):
+                raise ValueError("temporal_accumulate: motion must hold rows of 12 values, not %r" % (motion.shape,))
+            keep.append(motion)
+            a.motion, a.n_motion = N.ptr(motion), len(motion)
     a.max_history = int(max_history)
     a.flags = N.TEMPORAL_DEMODULATE if demodulate else 0
     a.normal_max, a.plane_max = float(normal_max), float(plane_max)
@@ -873,8 +894,9 @@ class TemporalHistory:
     """What srt_temporal_accumulate carries from one frame of a sequence to the next, in device memory of the
     process context (device_buffer / release_buffer): two sets of the accumulated half-frames and their lengths
     ("a", "b" (3, n), "len" (n,)) and of the frame's guides ("hit_id" int32, "position", "normal"), swapped every
-    frame -- the call reads one set and writes the other -- and the previous frame's camera.  reset(), and a
-    frame of another size, drop everything."""
+    frame -- the call reads one set and writes the other -- and the previous frame's camera.  With `motion` also a
+    copy of that frame's lowered collider table (host), from which the next frame's motion table is derived.
+    reset(), and a frame of another size, drop everything."""
 
     PLANES = (("a", 24), ("b", 24), ("len", 8), ("hit_id", 4), ("position", 24), ("normal", 24))  # bytes per pixel
 
@@ -882,6 +904,7 @@ class TemporalHistory:
         self.size = None      # (W, H) of the buffers
         self.cur = 0          # the set holding the previous frame
         self.prev_cam = None  # that frame's CameraDesc; None: no history
+        self.prev_colliders = None  # that frame's collider table if it was rendered with `motion`, else None
 
     def _name(self, k, s):
         return "temporal_%x_%s%d" % (id(self), k, s)
@@ -891,15 +914,22 @@ class TemporalHistory:
             for s in (0, 1):
                 for k, _ in self.PLANES:
                     release_buffer(self._name(k, s))
-        self.size, self.prev_cam, self.cur = None, None, 0
+            release_buffer(self._name("motion", 0))
+        self.size, self.prev_cam, self.cur, self.prev_colliders = None, None, 0, None
 
     def _set(self, s, n):
         return {k: device_buffer(self._name(k, s), bytes_pp * n) for k, bytes_pp in self.PLANES}
 
-    def accumulate(self, rgb_a, rgb_b, aovs, cam_desc, width, height, demodulate=False, timings=None, **params):
+    def accumulate(self, rgb_a, rgb_b, aovs, cam_desc, width, height, demodulate=False, timings=None, colliders=None,
+                   motion=False, **params):
         """One frame: the device half-frames `rgb_a`, `rgb_b` are accumulated in place against the history, which
         then becomes this frame's (`aovs`: device guides with "hit_id"; `cam_desc`: the frame's CameraDesc;
-        `params`: temporal_accumulate's max_history / normal_max / plane_max)."""
+        `params`: temporal_accumulate's max_history / normal_max / plane_max).  `motion` with `colliders`, the
+        frame's lowered collider table: the table of _motion.collider_motion against the previous frame's is
+        passed on -- when that frame left one, which a first frame, a frame after reset() and a frame rendered
+        without `motion` do not: this frame then runs without a table.  A copy is kept either way (the caller's
+        objects change in place).  Returns None, or (moved, unknown) rows of the table that was used ((0, 0):
+        none was)."""
         lib, ctx = context()
         W, H = int(width), int(height)
         n = W * H
@@ -907,16 +937,30 @@ class TemporalHistory:
             self.reset()
             self.size = (W, H)
         prev, nxt = self._set(self.cur, n), self._set(1 - self.cur, n)
+        table, counts = None, None
+        if motion:
+            if colliders is None:
+                raise ValueError("TemporalHistory.accumulate: motion needs the frame's collider table")
+            counts = (0, 0)
+            if self.prev_cam is not None and self.prev_colliders is not None:
+                rows = collider_motion(self.prev_colliders, colliders)
+                if len(rows):
+                    counts = count_rows(rows)
+                    dev = device_buffer(self._name("motion", 0), rows.nbytes)
+                    N.check(lib, lib.srt_memcpy(ctx, dev, N.ptr(rows), rows.nbytes))
+                    table = (dev, len(rows))
         temporal_accumulate(rgb_a, rgb_b, aovs, W, H, history=prev if self.prev_cam is not None else None,
                             prev_cam=self.prev_cam, demodulate=demodulate, timings=timings,
                             out={"a": rgb_a, "b": rgb_b, "hist_a": nxt["a"], "hist_b": nxt["b"], "len": nxt["len"]},
-                            **params)
+                            motion=table, **params)
+        self.prev_colliders = np.array(colliders, copy=True) if motion else None
         for k, bytes_pp in self.PLANES[3:]:  # this frame's guides are the next frame's history guides
             N.check(lib, lib.srt_memcpy(ctx, nxt[k], _addr(aovs[k]), bytes_pp * n))
         cam = N.CameraDesc()
         ctypes.memmove(ctypes.byref(cam), ctypes.byref(cam_desc), ctypes.sizeof(cam))
         cam.xs = cam.ys = None
         self.prev_cam, self.cur = cam, 1 - self.cur
+        return counts
 
     def __del__(self):
         try:

@@ -330,6 +330,8 @@ class TemporalArgs(ctypes.Structure):
         ("out_hist_b", _p),
         ("out_len", _p),
         ("ms_kernel", ctypes.POINTER(ctypes.c_double)),
+        ("motion", _p),
+        ("n_motion", ctypes.c_int32),
     ]
 
 

@@ -113,7 +113,15 @@ class Scene:
         0.1 and `"temporal_plane"` 0.02 are the two acceptance thresholds).  With `demodulate` the history holds
         colour / albedo.  The history lives in device memory with the scene; `reset_history()` drops it, as does
         a frame of another size.  Moving objects are reprojected as if static (their history is rejected where
-        the geometry changed).
+        the geometry changed) unless `"motion": True` is given too (a bool, off by default, ignored without
+        `temporal`): each pixel is then first mapped back by the rigid motion of the collider it sees, derived
+        from the collider tables of this frame and the one before (_motion.collider_motion), so a translated or
+        rotated Sphere, Plane, Cuboid or Triangle keeps its history; `last_stats["denoise"]` then holds
+        `motion_moved` and `motion_unknown`, the colliders that moved and those no rigid motion explains (a
+        changed size, a deformed mesh, a reordered or edited collider list: no history for them).  The first
+        frame, the frame after `reset_history()` and the frame after one rendered without `motion` run without
+        a table.  The guides are first-hit only: a moving object's shadow and its reflections in other objects
+        still lag.
         """
         from . import _backend as B
         from . import _hybrid
@@ -223,7 +231,8 @@ class Scene:
         t0 = time.time()
         H, W = int(self.camera.screen_height), int(self.camera.screen_width)
         temporal = params.get("temporal", False)
-        filt = {k: v for k, v in params.items() if k not in B.N.TEMPORAL_DEFAULTS}
+        motion = params.get("motion", False)
+        filt = {k: v for k, v in params.items() if k not in B.N.TEMPORAL_DEFAULTS and k != "motion"}
         extra = {}
         with B.DeviceArrays() as pool:
             A, Bh, ka, kb, stats = B.render_halves(self, samples_per_pixel, rng=rng, seed=seed, batch_size=batch_size,
@@ -234,10 +243,14 @@ class Scene:
                 if self._history is None:
                     self._history = B.TemporalHistory()
                 mt = []
-                self._history.accumulate(A, Bh, aovs, B.camera_desc(self.camera), W, H, demodulate=params["demodulate"],
-                                         timings=mt, max_history=params["max_history"],
-                                         normal_max=params["temporal_normal"], plane_max=params["temporal_plane"])
+                rows = self._history.accumulate(A, Bh, aovs, B.camera_desc(self.camera), W, H,
+                                                demodulate=params["demodulate"], timings=mt, colliders=aovs["colliders"],
+                                                motion=motion, max_history=params["max_history"],
+                                                normal_max=params["temporal_normal"], plane_max=params["temporal_plane"])
                 extra["ms_temporal"] = mt[0]
+                if motion:
+                    # rows of the motion table that moved, and that no rigid motion explains (0, 0 without a table)
+                    extra["motion_moved"], extra["motion_unknown"] = rows
             blk = B.image_block(4 * W * H)
             ms = []
             _, _, u8 = B.denoise_var(A, Bh, ka, kb, aovs, W, H, want_rgb=False, rgbx=True, out_u8=blk, timings=ms,

@@ -9,8 +9,13 @@ level as the yardstick, in one session:
    the same frame.  Also the share of surface pixels that found history.
 2. cornell at 800x800, 16 samples through Scene.render: variance + demodulate with and without "temporal", wall
    clock, alternating, --runs each (the temporal frames accumulate on one another under an unchanged camera).
+3. --motion (instead of 1 and 2): on the inputs of 1, the current frame's call with SRT_TEMPORAL_DEMODULATE without
+   a motion table (k_temporal<false>) and with an all-identity table of one row per collider (k_temporal<true>),
+   alternating, median of --repeats each.  The identity rows leave every tap where it is, so the two calls gather
+   the same history and differ by the row loads and the 18 multiply-adds per pixel alone.
 
     python tools/temporal_cost.py [--size 1920x1080] [--repeats 7] [--out profiles/temporal_cost.json]
+    python tools/temporal_cost.py --motion [--out profiles/temporal_motion_cost.json]
 """
 import argparse
 import json
@@ -76,6 +81,37 @@ def timed(B, dev, W, H, out, repeats, **kw):
             "gb_per_s_of_compulsory_traffic": round(bytes_pp * n / 1e9 / (m * 1e-3), 1)}
 
 
+def motion_leg(B, N, dev, hit_id, W, H, out, repeats, **kw):
+    """k_temporal<false> against k_temporal<true> with an identity table, alternating in one session."""
+    from sightpy._motion import IDENTITY
+
+    n = W * H
+    rows = np.tile(IDENTITY, (int(hit_id.max()) + 1, 1))
+    table = B.device_buffer("tcost_motion", rows.nbytes)
+    lib, ctx = B.context()
+    N.check(lib, lib.srt_memcpy(ctx, table, N.ptr(rows), rows.nbytes))
+    runs = {False: [], True: []}
+    lens = {}
+    for r in range(repeats + 1):
+        for on in (False, True):
+            ms = []
+            B.temporal_accumulate(dev["a"], dev["b"], dev, W, H, out=out, timings=ms,
+                                  motion=(table, len(rows)) if on else None, **kw)
+            runs[on].append(ms[0])
+            if r == 0:
+                with B.DeviceArrays() as pool:
+                    lens[on] = pool.fetch(out["len"], (n,))
+    res = {"rows": len(rows), "table_bytes": int(rows.nbytes), "same_out_len": bool(np.array_equal(lens[False], lens[True]))}
+    for on, name in ((False, "k_temporal<false>"), (True, "k_temporal<true> identity table")):
+        t = runs[on][1:]
+        m = median(t)
+        res[name] = {"ms_kernel": round(m, 4), "ms_spread": round(max(t) - min(t), 4),
+                     "gb_per_s_of_compulsory_traffic": round(COMPULSORY * n / 1e9 / (m * 1e-3), 1)}
+    res["true_over_false"] = round(res["k_temporal<true> identity table"]["ms_kernel"] / res["k_temporal<false>"]["ms_kernel"], 4)
+    B.release_buffer("tcost_motion")
+    return res
+
+
 def main():
     from sightpy import _backend as B, _native as N
     from sightpy._lower import camera_desc
@@ -85,6 +121,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--cornell", default="800x800:16", help="WxH:spp through Scene.render ('' skips it)")
     ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--motion", action="store_true", help="the motion leg alone (3. above)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     W, H = (int(v) for v in a.size.lower().split("x"))
@@ -92,6 +129,10 @@ def main():
     out = {"what": "srt_temporal_accumulate beside one k_atrous<true> level, ms by HIP events (median of %d runs, one "
                    "session)" % a.repeats, "size": [W, H],
            "bytes_per_pixel": {"compulsory": COMPULSORY, "first_frame": STREAM_IN + STORES, "worst_case": WORST}}
+    if a.motion:
+        out["what"] = ("srt_temporal_accumulate without a motion table and with an all-identity one, alternating, ms by "
+                       "HIP events (median of %d runs each, one session)" % a.repeats)
+        a.cornell = ""
     names = set()
     for name in ("example1", "cornell"):
         frames = {}
@@ -110,6 +151,10 @@ def main():
         B.temporal_accumulate(pdev["a"], pdev["b"], pdev, W, H, demodulate=True, out=sets[0])
         hist = {"a": sets[0]["hist_a"], "b": sets[0]["hist_b"], "len": sets[0]["len"], "hit_id": pdev["hit_id"],
                 "position": pdev["position"], "normal": pdev["normal"]}
+        if a.motion:
+            out[name] = motion_leg(B, N, cdev, np.asarray(aovs["hit_id"]), W, H, sets[1], a.repeats, history=hist,
+                                   prev_cam=pcam, demodulate=True)
+            continue
         res = {"demodulate=1": timed(B, cdev, W, H, sets[1], a.repeats, history=hist, prev_cam=pcam, demodulate=True)}
         with B.DeviceArrays() as pool:
             ln = pool.fetch(sets[1]["len"], (n,))
