@@ -749,7 +749,10 @@ def test_gpu_create_animation_frames(tmp_path, monkeypatch):
 @pytest.mark.parametrize("shape", [(1, 1), (67, 13), (13, 67), (129, 3)])
 def test_gpu_edge_shapes_match_oracle(shape, mode):
     """Frame shapes that leave partial waves / blocks / tiles everywhere (1x1, odd sizes) through
-    both trace strategies, against the oracle on the same jitter."""
+    both trace strategies, against the oracle on the same jitter; the uint8 image against the exact rule on
+    the kernel's own linear RGB (tests/resolve_ref.py: no rendered value is ambiguous, every byte is pinned)."""
+    import resolve_ref as R
+
     W, H = shape
     sc = scenes.example1(W, H, 3)
     np.random.seed(2)
@@ -763,6 +766,9 @@ def test_gpu_edge_shapes_match_oracle(shape, mode):
     assert np.array_equal(out.hit_ids, ids)
     assert out.stats["rays_per_depth"] == [counts["depth"][d] for d in sorted(counts["depth"])]
     np.testing.assert_allclose(out.rgb, rgb, rtol=RTOL, atol=ATOL)
+    lo, hi = R.bounds(out.rgb)
+    assert np.array_equal(lo, hi)
+    R.check_bytes(out.srgb8, lo, hi, "%s %dx%d" % (mode, W, H))
 
 
 @pytest.mark.parametrize("which", ["no_background", "background_only"])
