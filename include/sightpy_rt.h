@@ -36,6 +36,8 @@
  *                             reprojected half-frames accumulated over the earlier frames)
  *   srt_upload_scene       <- (scene lowering; the reference deep-copies the Scene per task,
  *                              scene.py:85)
+ *   srt_pose_colliders:    no counterpart (a TriangleMesh moved rigidly on the device: its collider records
+ *                             and the BVH's boxes recomputed from a resident copy of the rest pose)
  *
  * Conventions
  *   - Every entry point returns 0 on success or a negative SRT_ERR_* code; the message of the
@@ -355,6 +357,29 @@ int srt_destroy(srt_ctx* ctx);
  *     n-rank frame rehearsed). */
 int srt_set_option(srt_ctx* ctx, const char* key, int64_t value);
 int srt_upload_scene(srt_ctx* ctx, const srt_scene_desc* scene);
+/* srt_pose_colliders: no counterpart (the reference moves a mesh by rewriting its Python colliders).  Rigidly
+ * pose ranges of Triangle colliders of the resident scene on the device.  srt_upload_scene keeps a second copy of
+ * the collider table in device memory, the rest pose; this call rewrites the records of the colliders
+ * [first[r], first[r] + count[r]) in the table the kernels read from that copy under poses[r], then refits the
+ * boxes of the BVH over the posed vertices (its topology stays the uploaded scene's; the scene's other tables are
+ * untouched).  Poses are absolute, from the rest pose: calling twice with the same arguments changes nothing, and
+ * a collider in no range keeps what the last call (or the upload) gave it.
+ *   pose        12 doubles, R row-major then T (the layout of srt_temporal_accumulate's motion rows)
+ *   vertex      x'[k] = ((R[k][0] x + R[k][1] y) + R[k][2] z) + T[k], in this order, unfused
+ *   record      from p1', p2', p3' as sightpy's Triangle_Collider computes it: centroid ((p1' + p2') + p3') / 3,
+ *               normal = normalize(cross(p2' - p1', p3' - p1')), n31 = cross(p3' - p1', normal), n12 =
+ *               cross(p1' - p2', normal), n23 = cross(p2' - p3', normal); with SRT_CF_VNORMAL the vertex
+ *               normals normalize(R n_i) (the vertex sums without T); with either attribute flag d2, d3 from
+ *               the posed vectors; the uvs, type, flags, material and the other integer fields are copied
+ *   identity    R = I and T = 0 exactly copies the rest record
+ *   BVH         every slot box recomputed bottom-up, one launch per node height: a leaf's from its triangles'
+ *               vertex boxes inflated by 1e-9 (1 + max |coordinate|) and rounded outward to float (the build's
+ *               rules, so the identity gives the built nodes back), an inner slot's the union of its child's
+ * The call first waits for asynchronous frames in flight and returns after the device finished.  SRT_ERR_ARG: no
+ * scene resident, n_ranges < 1, a range outside the table or with count < 1 or covering a collider that is no
+ * Triangle, overlapping ranges, a pose entry that is not finite. */
+int srt_pose_colliders(srt_ctx* ctx, int32_t n_ranges, const int32_t* first, const int32_t* count,
+                       const double* poses /* [n_ranges][12] */);
 int srt_render(srt_ctx* ctx, const srt_camera* cam, const srt_render_args* args, srt_stats* stats);
 /* Queue the numpy-stream generation of the synchronous whole frame that srt_render will be called
  * for next with the same camera size and args (args->mt set, no rows, not SRT_RENDER_ASYNC /
@@ -685,6 +710,9 @@ int srt_debug_lane_stats(srt_ctx* ctx, int mode, int64_t* out, int n);
 /* Diagnostic: launches of the lean fused kernel (k_primary_lean: pipelined frames of single-child
  * scenes without a BVH, or any frame with option "sync_lean") since the context was created. */
 int srt_debug_lean_launches(srt_ctx* ctx, int64_t* launches);
+/* Diagnostic: device time of the last srt_pose_colliders call by HIP events (ms: the record kernel, the
+ * summed BVH refit launches) and the calls made since the context was created.  Any output may be NULL. */
+int srt_debug_pose_times(srt_ctx* ctx, double* ms_pose, double* ms_refit, int64_t* calls);
 const char* srt_last_error(void);
 
 #ifdef __cplusplus

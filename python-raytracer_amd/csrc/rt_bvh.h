@@ -15,7 +15,8 @@
 // more triangles) stays in the linear collider loop.  Boxes are the
 // triangles' vertex boxes inflated by 1e-9 * (1 + max |coordinate|) -- the reference intersects the
 // plane through the centroid and tests edge half-spaces with >= 0, so a hit point may sit a few ulps
-// outside the vertex box -- then rounded outward to float.
+// outside the vertex box -- then rounded outward to float.  These two rules are RT_HD helpers, shared with
+// the refit of a posed mesh's boxes on the device (rt_pose.h), which follows the node heights of bvh_levels.
 #pragma once
 
 #include <algorithm>
@@ -35,6 +36,47 @@ constexpr int BVH_MAX_DEPTH = 20;  // binary levels (so at most 10 4-wide levels
 static_assert(3 * ((BVH_MAX_DEPTH + 1) / 2) + 1 <= BVH_STACK, "traversal stack holds the deepest path");
 constexpr int BVH_LEAF_MAX = 63;            // triangles per leaf (6-bit count in the child code)
 constexpr int32_t BVH_SLOTS_MAX = 1 << 25;  // leaf slots (first << 6 fits the child code)
+
+// The two rules of a BVH box, shared by the build below and the refit kernel (rt_pose.h k_bvh_refit), so
+// that a refit over unchanged vertices gives the build's boxes bit for bit.
+// A triangle's box: its vertex box (p1 = p[6..8], p2 = p[9..11], p3 = p[12..14]) inflated by
+// 1e-9 * (1 + max |coordinate|).
+template <class P>
+RT_HD void bvh_triangle_box(P p, double* lo, double* hi) {
+    double m = 0.0;
+    for (int k = 0; k < 3; ++k) {
+        const double a = p[6 + k], b = p[9 + k], c = p[12 + k];
+        const double ab_lo = b < a ? b : a, ab_hi = a < b ? b : a;
+        lo[k] = c < ab_lo ? c : ab_lo;
+        hi[k] = ab_hi < c ? c : ab_hi;
+        const double al = fabs(lo[k]), ah = fabs(hi[k]);
+        const double mk = al < ah ? ah : al;
+        m = m < mk ? mk : m;
+    }
+    const double eps = 1e-9 * (1.0 + m);
+    for (int k = 0; k < 3; ++k) {
+        lo[k] -= eps;
+        hi[k] += eps;
+    }
+}
+// An f64 bound rounded outward to float.
+RT_HD float bvh_round_down(double x) {
+    float f = (float)x;
+    if ((double)f > x) f = nextafterf(f, -INFINITY);
+    return f;
+}
+RT_HD float bvh_round_up(double x) {
+    float f = (float)x;
+    if ((double)f < x) f = nextafterf(f, INFINITY);
+    return f;
+}
+
+// Node indices grouped by height (rt_pose.h k_bvh_refit runs once per group): a node whose slots are all
+// leaves or empty has height 0, any other one more than its highest child node.
+struct BvhLevels {
+    std::vector<int32_t> nodes;   // node indices, height 0 first
+    std::vector<int32_t> offset;  // group h is nodes[offset[h], offset[h + 1])
+};
 
 struct BvhBuild {
     std::vector<BvhNode> nodes;
@@ -75,19 +117,8 @@ inline void bvh_build(const srt_collider* col, int n, BvhBuild& out) {
     for (int i = 0; i < n; ++i)
         if (col[i].type == SRT_TRIANGLE) {
             Item it;
-            const double* p = col[i].p;  // p1 = p[6..8], p2 = p[9..11], p3 = p[12..14]
-            double m = 0.0;
-            for (int k = 0; k < 3; ++k) {
-                it.lo[k] = std::min(std::min(p[6 + k], p[9 + k]), p[12 + k]);
-                it.hi[k] = std::max(std::max(p[6 + k], p[9 + k]), p[12 + k]);
-                m = std::max(m, std::max(std::fabs(it.lo[k]), std::fabs(it.hi[k])));
-            }
-            const double eps = 1e-9 * (1.0 + m);
-            for (int k = 0; k < 3; ++k) {
-                it.lo[k] -= eps;
-                it.hi[k] += eps;
-                it.c[k] = 0.5 * (it.lo[k] + it.hi[k]);
-            }
+            bvh_triangle_box(col[i].p, it.lo, it.hi);
+            for (int k = 0; k < 3; ++k) it.c[k] = 0.5 * (it.lo[k] + it.hi[k]);
             it.col = i;
             items.push_back(it);
         }
@@ -192,16 +223,6 @@ inline void bvh_build(const srt_collider* col, int n, BvhBuild& out) {
         tasks.push_back({left + 1, mid, t.end, t.depth + 1});
     }
     // collapse into 4-wide nodes (node 0 = the root's children)
-    auto fdown = [](double x) {
-        float f = (float)x;
-        if ((double)f > x) f = std::nextafter(f, -INFINITY);
-        return f;
-    };
-    auto fup = [](double x) {
-        float f = (float)x;
-        if ((double)f < x) f = std::nextafter(f, INFINITY);
-        return f;
-    };
     if (bin[0].count > 0) {  // a single leaf (not reached: BVH_MIN_TRIANGLES > BVH_LEAF)
         bin.push_back(bin[0]);
         bin[0].first = (int32_t)bin.size() - 1;
@@ -242,8 +263,8 @@ inline void bvh_build(const srt_collider* col, int n, BvhBuild& out) {
             }
             const BinNode& c = bin[slots[k]];
             for (int a = 0; a < 3; ++a) {
-                nd4.lo[a][k] = fdown(c.lo[a]);
-                nd4.hi[a][k] = fup(c.hi[a]);
+                nd4.lo[a][k] = bvh_round_down(c.lo[a]);
+                nd4.hi[a][k] = bvh_round_up(c.hi[a]);
             }
             if (c.count > 0) {
                 nd4.child[k] = -(c.first + 1);
@@ -270,6 +291,26 @@ inline void bvh_build(const srt_collider* col, int n, BvhBuild& out) {
             if (nd.child[k] != BVH_EMPTY)
                 for (int a = 0; a < 3; ++a)
                     out.bound = std::max(out.bound, std::max(std::fabs(nd.lo[a][k]), std::fabs(nd.hi[a][k])));
+}
+
+// The refit order of a built tree (child nodes have higher indices than their parent: one reverse pass).
+inline void bvh_levels(const std::vector<BvhNode>& nodes, BvhLevels& out) {
+    const int n = (int)nodes.size();
+    std::vector<int> height((size_t)n, 0);
+    int top = -1;
+    for (int i = n - 1; i >= 0; --i) {
+        int h = 0;
+        for (int k = 0; k < 4; ++k)
+            if (nodes[i].child[k] >= 0) h = std::max(h, height[nodes[i].child[k]] + 1);
+        height[i] = h;
+        top = std::max(top, h);
+    }
+    out.offset.assign((size_t)top + 2, 0);
+    for (int i = 0; i < n; ++i) out.offset[height[i] + 1]++;
+    for (int h = 0; h <= top; ++h) out.offset[h + 1] += out.offset[h];
+    out.nodes.assign((size_t)n, 0);
+    std::vector<int32_t> at(out.offset.begin(), out.offset.end() - 1);
+    for (int i = 0; i < n; ++i) out.nodes[at[height[i]]++] = i;
 }
 
 }  // namespace rt

@@ -14,6 +14,7 @@
 #include "rt_denoise.h"
 #include "rt_device.h"
 #include "rt_mt.h"
+#include "rt_pose.h"
 
 using namespace rt;
 
@@ -544,6 +545,81 @@ void hc_xpow_mod(uint64_t J, uint32_t* out) {
 void hc_jump_window(const uint32_t* key, uint64_t J, uint32_t* out) {
     const std::vector<uint32_t> p = rtmt::xpow_mod(J);
     rtmt::jump_serial(key, p.data(), out);
+}
+
+// ---- posed triangle meshes (rt_pose.h) ----
+// the records rec[0, n) under one pose, as k_pose_triangles writes them
+void hc_pose_triangles(const srt_collider* rec, int n, const double* pose, srt_collider* out) {
+    for (int i = 0; i < n; ++i) pose_triangle_record(rec[i], pose, out[i]);
+}
+
+namespace {
+// srt_pose_colliders on the host: `col` (the scene's table, a copy) posed range by range, then the built
+// tree `B` refitted height by height and its bound recomputed as the library recomputes it
+void pose_and_refit(const srt_scene_desc* d, int n_ranges, const int32_t* first, const int32_t* count,
+                    const double* poses, std::vector<srt_collider>& col, BvhBuild& B) {
+    std::vector<uint8_t> posed(col.size(), 0);
+    double reach = 0.0;
+    bool all_identity = true;
+    for (int r = 0; r < n_ranges; ++r) {
+        const double* pose = poses + (size_t)r * POSE_DOUBLES;
+        double box[6];
+        pose_range_box(d->colliders, first[r], count[r], box);
+        reach = std::max(reach, pose_box_reach(box, box + 3, pose));
+        all_identity = all_identity && pose_is_identity(pose);
+        for (int i = first[r]; i < first[r] + count[r]; ++i) {
+            pose_triangle_record(d->colliders[i], pose, col[i]);
+            posed[i] = 1;
+        }
+    }
+    if (B.nodes.empty()) return;
+    BvhLevels lv;
+    bvh_levels(B.nodes, lv);
+    for (size_t h = 0; h + 1 < lv.offset.size(); ++h)
+        for (int j = lv.offset[h]; j < lv.offset[h + 1]; ++j)
+            for (int k = 0; k < 4; ++k) bvh_refit_slot(B.nodes.data(), B.tri.data(), col.data(), lv.nodes[j], k);
+    if (!all_identity)
+        B.bound = pose_bound(std::max(reach, pose_static_reach(d->colliders, d->n_colliders, posed.data())));
+}
+}  // namespace
+
+// The 4-wide nodes of `d`'s BVH after srt_pose_colliders' two steps on the host (n_ranges 0: as built).
+// Returns the node count; up to cap_nodes nodes (128 bytes each, rt_device.h BvhNode) go to `nodes`, up to
+// cap_tri leaf slots (collider indices) to `tri`, the posed table (d->n_colliders records) to `posed`, the
+// traversal's bound to `bound`; each may be NULL.
+int hc_bvh_refit(const srt_scene_desc* d, int n_ranges, const int32_t* first, const int32_t* count,
+                 const double* poses, void* nodes, int cap_nodes, int32_t* tri, int cap_tri, srt_collider* posed,
+                 float* bound) {
+    BvhBuild B;
+    bvh_build(d->colliders, d->n_colliders, B);
+    std::vector<srt_collider> col(d->colliders, d->colliders + d->n_colliders);
+    if (n_ranges > 0) pose_and_refit(d, n_ranges, first, count, poses, col, B);
+    if (nodes && !B.nodes.empty())
+        memcpy(nodes, B.nodes.data(), sizeof(BvhNode) * (size_t)std::min<int>(cap_nodes, (int)B.nodes.size()));
+    if (tri && !B.tri.empty()) memcpy(tri, B.tri.data(), 4 * (size_t)std::min<int>(cap_tri, (int)B.tri.size()));
+    if (posed && !col.empty()) memcpy(posed, col.data(), sizeof(srt_collider) * col.size());
+    if (bound) *bound = B.bound;
+    return (int)B.nodes.size();
+}
+
+// hc_nearest on the posed scene: through the refitted BVH, or (hc_set_bvh(0)) the linear loop over the posed table
+int hc_pose_nearest(const srt_scene_desc* d, int n_ranges, const int32_t* first, const int32_t* count,
+                    const double* poses, const double* O, const double* D, int64_t n, double* t, int32_t* id,
+                    double* orient) {
+    SceneView S = view_of(d);
+    std::vector<srt_collider> col(d->colliders, d->colliders + d->n_colliders);
+    pose_and_refit(d, n_ranges, first, count, poses, col, g_bvh);
+    S.col = col.data();
+    S.bvh_bound = g_bvh.bound;
+    for (int64_t i = 0; i < n; ++i) {
+        double tn, on;
+        bool ties;
+        int c = nearest_hit(S, d3{O[i], O[n + i], O[2 * n + i]}, d3{D[i], D[n + i], D[2 * n + i]}, tn, on, ties);
+        if (t) t[i] = tn;
+        if (id) id[i] = c;
+        if (orient) orient[i] = on;
+    }
+    return SRT_OK;
 }
 
 }  // extern "C"

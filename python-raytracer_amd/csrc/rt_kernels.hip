@@ -7,8 +7,9 @@
 //   rt_variants.h       MATS_*, Variant, VARIANTS, SEQ_VARIANTS, pick_variant
 //   rt_aux_kernels.h    k_pass_end, k_resolve, the API kernels, k_assemble, k_rgbx, k_seed_queue, k_gather_children
 //   rt_devmem.h         DevBuf / DevList, dalloc, grid_for
+//   (rt_pose.h, with the headers above: pose_triangle_record, k_pose_triangles, k_bvh_refit)
 //   (this file)         the context and its frame slots, the MT host side, frame collection and gather,
-//                       srt_create and the options, scene upload
+//                       srt_create and the options, scene upload, srt_pose_colliders
 //   rt_render.h         render_impl, before srt_render and its siblings
 //   rt_api_trace.h      trace_impl, srt_trace and srt_shade*
 //   rt_api_entry.h      the single-kernel entry points, AOVs and denoise, device memory, srt_mt19937_uniforms
@@ -59,6 +60,7 @@
 #include "rt_denoise.h"
 #include "rt_mt.h"
 #include "rt_mt_kernel.h"
+#include "rt_pose.h"
 
 using namespace rt;
 using namespace rtmt_dev;
@@ -167,6 +169,28 @@ struct srt_ctx {
     int n_user_lights = 0;
     bool needs_inputs = false;
     DevList scene_bufs;
+    // posed triangle meshes (srt_pose_colliders, rt_pose.h).  In scene_bufs: the collider table the kernels
+    // read (S.col), its copy in the pose it was uploaded in, the BVH's nodes and leaf slots as plain pointers,
+    // the nodes grouped by height (rt_bvh.h BvhLevels).  On the host: the uploaded table, the groups' offsets,
+    // the built tree's bvh_bound, and what the last call derived from its ranges alone
+    srt_collider* col_live = nullptr;
+    srt_collider* col_rest = nullptr;
+    BvhNode* bvh_dev = nullptr;
+    int32_t* bvh_tri_dev = nullptr;
+    int32_t* bvh_level_nodes = nullptr;
+    int bvh_ntri = 0;
+    std::vector<int32_t> bvh_level_offset;
+    std::vector<srt_collider> col_host;
+    float bvh_bound_rest = 0.0f;
+    struct PoseLayout {
+        std::vector<int32_t> key;                   // first, count per range: valid for these
+        std::vector<std::array<double, 6>> box;     // rest vertex box per range
+        double static_reach = 0.0;                  // max |coordinate| of the triangles in no range
+    } pose_layout;
+    DevBuf<PoseRange> pose_ranges;
+    hipEvent_t pose_ev[3] = {nullptr, nullptr, nullptr};  // start, after k_pose_triangles, after the refit
+    double pose_ms[2] = {0.0, 0.0};                       // (srt_debug_pose_times) of the last call
+    int64_t pose_calls = 0;
     // texel pool (outside scene_bufs: survives re-uploads with the same texel_key)
     DevBuf<uint8_t> texels;
     uint64_t texel_key = 0;
@@ -1031,6 +1055,8 @@ srt_ctx::~srt_ctx() {
     scene_bufs.clear();
     if (comm) (void)ncclCommDestroy(comm);
     if (mt_done) (void)hipEventDestroy(mt_done);
+    for (hipEvent_t e : pose_ev)
+        if (e) (void)hipEventDestroy(e);
     if (mt_stream) (void)hipStreamDestroy(mt_stream);
 }
 
@@ -1325,6 +1351,8 @@ static int upload_tables(srt_ctx* c, const srt_scene_desc* d, SceneView& S, bool
     srt_light* lights;
     double *media, *f0, *ll, *imp;
     if ((rc = upload(c, d->colliders, d->n_colliders, &col))) return rc;
+    c->col_live = col;
+    c->col_host.assign(d->colliders, d->colliders + std::max(0, d->n_colliders));
     if ((rc = upload(c, d->materials, d->n_materials, &mat))) return rc;
     const TexelPool tp = plan_texel_pool(d, d->texel_bytes > 0 && d->texels && !is_device_ptr(d->texels));
     if ((rc = upload(c, tp.tex.data(), d->n_textures, &tex))) return rc;
@@ -1358,6 +1386,17 @@ static int upload_tables(srt_ctx* c, const srt_scene_desc* d, SceneView& S, bool
     if ((rc = upload(c, B.lin.data(), (int64_t)B.lin.size(), &lin))) return rc;
     if ((rc = upload(c, B.tri.data(), (int64_t)B.tri.size(), &tri))) return rc;
     if ((rc = upload(c, B.nodes.data(), (int64_t)B.nodes.size(), &nodes))) return rc;
+    // what srt_pose_colliders needs, after every table the trace kernels read (whose allocations, and so
+    // addresses, stay what they were without it): the rest pose's copy of the collider table, the refit order
+    if ((rc = upload(c, d->colliders, d->n_colliders, &c->col_rest))) return rc;
+    BvhLevels lv;
+    bvh_levels(B.nodes, lv);
+    if ((rc = upload(c, lv.nodes.data(), (int64_t)lv.nodes.size(), &c->bvh_level_nodes))) return rc;
+    c->bvh_level_offset = lv.offset;
+    c->bvh_dev = nodes;
+    c->bvh_tri_dev = tri;
+    c->bvh_ntri = (int)B.tri.size();
+    c->bvh_bound_rest = B.bound;
     S.nlin = (int)B.lin.size();
     S.lin = (decltype(S.lin))lin;
     S.bvh_tri = (decltype(S.bvh_tri))tri;
@@ -1429,11 +1468,111 @@ int srt_upload_scene(srt_ctx* c, const srt_scene_desc* d) {
     HIP_TRY(hipStreamSynchronize(c->f->stream));
     c->scene_bufs.clear();
     c->has_scene = false;
+    c->col_live = c->col_rest = nullptr;
+    c->bvh_dev = nullptr;
+    c->bvh_tri_dev = c->bvh_level_nodes = nullptr;
+    c->bvh_level_offset.clear();
+    c->pose_layout = srt_ctx::PoseLayout{};
     SceneView S{};
     bool lin_tri = false;
     if ((rc = upload_tables(c, d, S, lin_tri))) return rc;
     derive_scene_facts(c, d, S, lin_tri);
     c->has_scene = true;
+    return SRT_OK;
+}
+
+// ---- srt_pose_colliders ----
+// what depends on the ranges alone, made once per set of ranges: their checks against the table (inside it,
+// triangles only, no overlap), each range's rest vertex box, the reach of the triangles in no range
+static int pose_layout_for(srt_ctx* c, int32_t n_ranges, const int32_t* first, const int32_t* count) {
+    std::vector<int32_t> key;
+    for (int r = 0; r < n_ranges; ++r) key.insert(key.end(), {first[r], count[r]});
+    srt_ctx::PoseLayout& PL = c->pose_layout;
+    if (!PL.key.empty() && PL.key == key) return SRT_OK;
+    PL = srt_ctx::PoseLayout{};
+    const int ncol = (int)c->col_host.size();
+    std::vector<uint8_t> posed((size_t)ncol, 0);
+    std::vector<std::array<double, 6>> box((size_t)n_ranges);
+    for (int r = 0; r < n_ranges; ++r) {
+        if (first[r] < 0 || count[r] < 1 || (int64_t)first[r] + count[r] > ncol)
+            return fail(SRT_ERR_ARG, "srt_pose_colliders: a range lies outside the collider table");
+        for (int i = first[r]; i < first[r] + count[r]; ++i) {
+            if (c->col_host[i].type != SRT_TRIANGLE)
+                return fail(SRT_ERR_ARG, "srt_pose_colliders: a range covers a collider that is no Triangle");
+            if (posed[i]) return fail(SRT_ERR_ARG, "srt_pose_colliders: the ranges overlap");
+            posed[i] = 1;
+        }
+        pose_range_box(c->col_host.data(), first[r], count[r], box[r].data());
+    }
+    PL.static_reach = pose_static_reach(c->col_host.data(), ncol, posed.data());
+    PL.key = std::move(key);
+    PL.box = std::move(box);
+    return SRT_OK;
+}
+
+int srt_pose_colliders(srt_ctx* c, int32_t n_ranges, const int32_t* first, const int32_t* count, const double* poses) {
+    if (!c) return fail(SRT_ERR_ARG, "srt_pose_colliders: null ctx");
+    if (!c->has_scene || !c->col_live || !c->col_rest) return fail(SRT_ERR_ARG, "srt_pose_colliders: no scene is resident");
+    if (n_ranges < 1 || !first || !count || !poses) return fail(SRT_ERR_ARG, "srt_pose_colliders: needs n_ranges >= 1 ranges and their poses");
+    for (int64_t k = 0; k < (int64_t)n_ranges * POSE_DOUBLES; ++k)
+        if (!std::isfinite(poses[k])) return fail(SRT_ERR_ARG, "srt_pose_colliders: a pose entry is not finite");
+    int rc;
+    if ((rc = pose_layout_for(c, n_ranges, first, count))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = finish_async(c, nullptr))) return rc;  // frames in flight read the tables rewritten below
+    const hipStream_t st = c->f->stream;
+    HIP_TRY(hipStreamSynchronize(st));
+    for (hipEvent_t& e : c->pose_ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    std::vector<PoseRange> R((size_t)n_ranges);
+    int64_t total = 0;
+    bool all_identity = true;
+    double reach = c->pose_layout.static_reach;
+    for (int r = 0; r < n_ranges; ++r) {
+        R[r].first = first[r];
+        R[r].count = count[r];
+        R[r].start = total;
+        total += count[r];
+        memcpy(R[r].pose, poses + (size_t)r * POSE_DOUBLES, sizeof R[r].pose);
+        all_identity = all_identity && pose_is_identity(R[r].pose);
+        const std::array<double, 6>& b = c->pose_layout.box[r];
+        reach = std::max(reach, pose_box_reach(b.data(), b.data() + 3, R[r].pose));
+    }
+    if ((rc = c->pose_ranges.ensure(n_ranges))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->pose_ranges, R.data(), R.size() * sizeof(PoseRange), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(c->pose_ev[0], st));
+    hipLaunchKernelGGL(k_pose_triangles, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, c->col_rest,
+                       c->col_live, c->pose_ranges.p, n_ranges, total, (int)c->col_host.size());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->pose_ev[1], st));
+    if (c->S.bvh_nodes > 0) {
+        // height by height, leaves' parents first: a group reads the boxes the groups before it wrote
+        for (size_t h = 0; h + 1 < c->bvh_level_offset.size(); ++h) {
+            const int off = c->bvh_level_offset[h], n = c->bvh_level_offset[h + 1] - off;
+            if (n <= 0) continue;
+            hipLaunchKernelGGL(k_bvh_refit, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, st, c->bvh_dev,
+                               c->S.bvh_nodes, c->bvh_tri_dev, c->bvh_ntri, c->col_live, (int)c->col_host.size(),
+                               c->bvh_level_nodes + off, n);
+            HIP_TRY(hipGetLastError());
+        }
+        c->S.bvh_bound = all_identity ? c->bvh_bound_rest : pose_bound(reach);
+    }
+    HIP_TRY(hipEventRecord(c->pose_ev[2], st));
+    HIP_TRY(hipStreamSynchronize(st));  // the next frame may run on another slot's stream
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->pose_ev[0], c->pose_ev[1]));
+    c->pose_ms[0] = ms;
+    HIP_TRY(hipEventElapsedTime(&ms, c->pose_ev[1], c->pose_ev[2]));
+    c->pose_ms[1] = ms;
+    c->pose_calls++;
+    return SRT_OK;
+}
+
+int srt_debug_pose_times(srt_ctx* c, double* ms_pose, double* ms_refit, int64_t* calls) {
+    if (!c) return fail(SRT_ERR_ARG, "null ctx");
+    if (ms_pose) *ms_pose = c->pose_ms[0];
+    if (ms_refit) *ms_refit = c->pose_ms[1];
+    if (calls) *calls = c->pose_calls;
     return SRT_OK;
 }
 

@@ -10,11 +10,14 @@ import os
 import numpy as np
 
 from . import _native as N
-from ._lower import lower_scene, camera_desc, collider_record
-from ._motion import collider_motion, count_rows
+from ._lower import lower_scene, camera_desc, collider_record, POSE_IDENTITY
+from ._motion import collider_motion, count_rows, pose_motion
 from .utils.vector3 import vec3
 
 _STATE = {"lib": None, "ctx": None, "device": None, "scene_sig": {}, "scene_inputs": {}, "buffers": {}, "pinned": {}, "group": None}
+# device-posed meshes (TriangleMesh.set_pose): the poses resident per context, and how often upload() called
+# srt_upload_scene and srt_pose_colliders
+_STATE.update({"pose_sig": {}, "uploads": 0, "pose_calls": 0})
 
 
 class RenderResult:
@@ -113,23 +116,45 @@ def group():
     return lib, ctxs
 
 
+def _pose_sig(posed, identity=False):
+    """What srt_pose_colliders would be called with for a Lowered's `posed` list, as a comparable value."""
+    return tuple((p["first"], p["count"], (POSE_IDENTITY if identity else p["pose"]).tobytes()) for p in posed)
+
+
 def upload(scene, extra_media=(), force=False, ctx=None):
     """Lower and upload `scene` to `ctx` (default: the process context) unless the identical tables
-    are already resident there."""
+    are already resident there.  The poses of device-posed meshes (TriangleMesh.set_pose) are no part of the
+    tables and are compared on their own: when only they changed, srt_pose_colliders alone is called
+    (_STATE["uploads"] and _STATE["pose_calls"] count the two kinds of call)."""
     lib = library()
     if ctx is None:
         ctx = context()[1]
     L = lower_scene(scene, extra_media)
     sig = L.signature()
     key = ctx.value if isinstance(ctx, ctypes.c_void_p) else int(ctx)
+    want = _pose_sig(L.posed)
+    if want != _pose_sig(L.posed, identity=True) and len(devices()) > 1:
+        raise NotImplementedError("a posed TriangleMesh (set_pose) renders on one GPU; %d are selected "
+                                  "($SIGHTPY_DEVICES)" % len(devices()))
     if force or sig != _STATE["scene_sig"].get(key):
         _STATE["scene_sig"].pop(key, None)
+        _STATE["pose_sig"].pop(key, None)
         N.check(lib, lib.srt_upload_scene(ctx, ctypes.byref(L.desc())))
+        _STATE["uploads"] += 1
         _STATE["scene_sig"][key] = sig
+        _STATE["pose_sig"][key] = _pose_sig(L.posed, identity=True)  # (an upload leaves every mesh in its rest pose)
         # a scene shaded with per-hit inputs (a user texture / Light, _hybrid.py): the library refuses
         # every whole-frame entry point on it, srt_render_prefetch included
         _STATE["scene_inputs"][key] = bool((L.materials["flags"] & N.MF_HIT_ALBEDO).any()
                                            or (L.lights["type"] == N.LIGHT_USER).any())
+    if want != _STATE["pose_sig"].get(key, ()):
+        _STATE["pose_sig"].pop(key, None)
+        first = np.array([p["first"] for p in L.posed], dtype=np.int32)
+        count = np.array([p["count"] for p in L.posed], dtype=np.int32)
+        poses = np.ascontiguousarray([p["pose"] for p in L.posed], dtype=np.float64)
+        N.check(lib, lib.srt_pose_colliders(ctx, len(first), N.ptr(first), N.ptr(count), N.ptr(poses)))
+        _STATE["pose_calls"] += 1
+        _STATE["pose_sig"][key] = want
     return L
 
 
@@ -693,6 +718,7 @@ def render_aovs_device(scene, pool, hit_id=False):
     res["ms_kernel"] = float(out.ms_kernel)
     if hit_id:
         res["colliders"] = L.colliders
+        res["posed"] = L.posed
     return res
 
 
@@ -905,6 +931,7 @@ class TemporalHistory:
         self.cur = 0          # the set holding the previous frame
         self.prev_cam = None  # that frame's CameraDesc; None: no history
         self.prev_colliders = None  # that frame's collider table if it was rendered with `motion`, else None
+        self.prev_posed = []        # ... and its device-posed meshes (Lowered.posed)
 
     def _name(self, k, s):
         return "temporal_%x_%s%d" % (id(self), k, s)
@@ -915,20 +942,22 @@ class TemporalHistory:
                 for k, _ in self.PLANES:
                     release_buffer(self._name(k, s))
             release_buffer(self._name("motion", 0))
-        self.size, self.prev_cam, self.cur, self.prev_colliders = None, None, 0, None
+        self.size, self.prev_cam, self.cur, self.prev_colliders, self.prev_posed = None, None, 0, None, []
 
     def _set(self, s, n):
         return {k: device_buffer(self._name(k, s), bytes_pp * n) for k, bytes_pp in self.PLANES}
 
     def accumulate(self, rgb_a, rgb_b, aovs, cam_desc, width, height, demodulate=False, timings=None, colliders=None,
-                   motion=False, **params):
+                   motion=False, posed=(), **params):
         """One frame: the device half-frames `rgb_a`, `rgb_b` are accumulated in place against the history, which
         then becomes this frame's (`aovs`: device guides with "hit_id"; `cam_desc`: the frame's CameraDesc;
         `params`: temporal_accumulate's max_history / normal_max / plane_max).  `motion` with `colliders`, the
         frame's lowered collider table: the table of _motion.collider_motion against the previous frame's is
         passed on -- when that frame left one, which a first frame, a frame after reset() and a frame rendered
         without `motion` do not: this frame then runs without a table.  A copy is kept either way (the caller's
-        objects change in place).  Returns None, or (moved, unknown) rows of the table that was used ((0, 0):
+        objects change in place).  `posed`: the frame's device-posed meshes (Lowered.posed), whose table records
+        stay in the rest pose: their rows come from the pose pair of the two frames (_motion.pose_motion).
+        Returns None, or (moved, unknown) rows of the table that was used ((0, 0):
         none was)."""
         lib, ctx = context()
         W, H = int(width), int(height)
@@ -944,6 +973,7 @@ class TemporalHistory:
             counts = (0, 0)
             if self.prev_cam is not None and self.prev_colliders is not None:
                 rows = collider_motion(self.prev_colliders, colliders)
+                pose_motion(rows, self.prev_posed, posed)
                 if len(rows):
                     counts = count_rows(rows)
                     dev = device_buffer(self._name("motion", 0), rows.nbytes)
@@ -954,6 +984,7 @@ class TemporalHistory:
                             out={"a": rgb_a, "b": rgb_b, "hist_a": nxt["a"], "hist_b": nxt["b"], "len": nxt["len"]},
                             motion=table, **params)
         self.prev_colliders = np.array(colliders, copy=True) if motion else None
+        self.prev_posed = [dict(p, pose=p["pose"].copy()) for p in posed] if motion else []
         for k, bytes_pp in self.PLANES[3:]:  # this frame's guides are the next frame's history guides
             N.check(lib, lib.srt_memcpy(ctx, nxt[k], _addr(aovs[k]), bytes_pp * n))
         cam = N.CameraDesc()

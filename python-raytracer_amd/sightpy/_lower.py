@@ -69,6 +69,11 @@ class Lowered:
         self.scene_n = None
         self.texel_key = 0
         self.device_index = []  # scene.collider_list index -> device collider index (-1: a user class, _hybrid)
+        # device-posed meshes (TriangleMesh.set_pose): one dict per mesh, "first" / "count" (its range of device
+        # collider indices), "pose" (12 float64, R row-major then T; the identity in the rest pose) and "key"
+        # ((id(mesh), its invalidate() count): equal keys in two frames name the same rest geometry).  The
+        # collider table holds such a mesh in its rest pose; the poses are no part of signature()
+        self.posed = []
 
     def light_table(self):
         """The srt_light records (N.LIGHT_DTYPE) of `lights` and `light_ext`."""
@@ -341,6 +346,31 @@ def collider_record(c):
     return rec
 
 
+POSE_IDENTITY = np.array([1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0])
+
+
+def _posed_span(prim, colliders, i):
+    """The length of the run colliders[i:] that is the whole collider list of `prim`, a device-posed
+    TriangleMesh (first and last collider checked: Scene.add appends a primitive's list as one run), else 0."""
+    if not getattr(prim, "_device_posed", False):
+        return 0
+    own = prim.collider_list
+    n = len(own)
+    if n == 0 or i + n > len(colliders) or colliders[i] is not own[0] or colliders[i + n - 1] is not own[-1]:
+        return 0
+    return n
+
+
+def _mesh_records(mesh):
+    """collider_record of every collider of a device-posed mesh, cached on the mesh until its invalidate()."""
+    if mesh._record_cache is None or len(mesh._record_cache) != len(mesh.collider_list):
+        recs = np.zeros(len(mesh.collider_list), dtype=N.COLLIDER_DTYPE)
+        for k, c in enumerate(mesh.collider_list):
+            recs[k] = collider_record(c)
+        mesh._record_cache = recs
+    return mesh._record_cache
+
+
 def camera_desc(cam):
     """srt_camera for a Camera (pointers into cam.xs / cam.ys)."""
     d = N.CameraDesc()
@@ -496,8 +526,40 @@ def lower_scene(scene, extra_media=()):
     shadow_ids = {id(c) for c in scene.shadowed_collider_list}
     crecs = np.zeros(len(colliders), dtype=N.COLLIDER_DTYPE)
     prim_index = {}
+    skip_to = 0
     for i, c in enumerate(colliders):
+        if i < skip_to:
+            continue
         prim = c.assigned_primitive
+        span = _posed_span(prim, colliders, i)
+        if span:
+            # a device-posed mesh: its rest records from the cache on the mesh, the per-scene fields filled in
+            # for the whole range at once
+            if hybrid and prim._pose is not None:
+                raise NotImplementedError(
+                    "a posed TriangleMesh (set_pose) in a scene with user Collider / Material / texture / Light "
+                    "subclasses: that path reads the Python colliders, which keep the rest pose")
+            recs = _mesh_records(prim)
+            m = prim.material
+            vuv = bool((recs["flags"] & N.CF_VUV).all())
+            if (getattr(m, "normalmap_u8", None) is not None
+                    or (isinstance(getattr(m, "diff_texture", None), image) and user_texture(m) is None and not vuv)
+                    or isinstance(m, ThinFilmInterference)):
+                raise NotImplementedError("Triangle uv is undefined in the reference (triangle.py:79-83)")
+            flags = 0
+            if id(c) in shadow_ids:
+                flags |= N.CF_SHADOW
+            if getattr(prim, "mc", False):
+                flags |= N.CF_MC
+            crecs[i:i + span] = recs
+            crecs["material"][i:i + span] = mat_index[id(m)]
+            crecs["max_ray_depth"][i:i + span] = int(prim.max_ray_depth)
+            crecs["flags"][i:i + span] |= flags
+            crecs["primitive"][i:i + span] = prim_index.setdefault(id(prim), len(prim_index))
+            L.posed.append({"first": i, "count": span, "key": (id(prim), prim._epoch),
+                            "pose": POSE_IDENTITY.copy() if prim._pose is None else prim._pose.copy()})
+            skip_to = i + span
+            continue
         rec = collider_record(c)
         rec["material"] = mat_index[id(prim.material)]
         rec["max_ray_depth"] = int(prim.max_ray_depth)

@@ -82,6 +82,29 @@ def collider_motion(prev_table, cur_table):
     return out
 
 
+def pose_motion(rows, prev_posed, cur_posed):
+    """Overwrite, in `rows` (collider_motion's table of the two frames), the rows of the device-posed meshes of
+    the current frame (`cur_posed`, `prev_posed`: the Lowered.posed lists of the two frames).  Such a mesh's records
+    are its rest pose in both tables, so collider_motion calls it static; its motion is the pose pair's: a
+    point x of the current frame was at R_prev R_cur^T (x - T_cur) + T_prev (R_cur is a rotation: its inverse
+    is its transpose), the same row for every collider of the mesh -- the records are not looked at.  Equal
+    poses give the identity row exactly.  A mesh without an entry of the same key and range in `prev_posed`
+    (first posed in this frame, invalidated or moved in the list since) gets NaN rows."""
+    prev = {p["key"]: p for p in prev_posed}
+    for cur in cur_posed:
+        sl = slice(cur["first"], cur["first"] + cur["count"])
+        old = prev.get(cur["key"])
+        if old is None or (old["first"], old["count"]) != (cur["first"], cur["count"]):
+            rows[sl] = np.nan
+        elif np.array_equal(old["pose"], cur["pose"]):
+            rows[sl] = IDENTITY
+        else:
+            Rp, Rc = old["pose"][:9].reshape(3, 3), cur["pose"][:9].reshape(3, 3)
+            R = Rp @ Rc.T
+            rows[sl] = np.concatenate([R.reshape(-1), old["pose"][9:] - R @ cur["pose"][9:]])
+    return rows
+
+
 def count_rows(motion):
     """(moved, unknown) of a table: rows that are neither the identity nor NaN, and rows holding a NaN."""
     unknown = np.isnan(motion).any(axis=1)

@@ -14,6 +14,11 @@ normalised sum of the unnormalised face cross products over the faces sharing th
 face normal where that sum is zero).  `texcoords=True` gives every triangle the `vt` coordinates its
 corners name (`v/vt`, `v/vt/vn`), so image textures can be applied; a face without them is a
 ValueError.  With the defaults the `vn` / `vt` records and indices are ignored, as before.
+
+`set_pose(R, t)` moves the mesh rigidly on the device (no reference counterpart): the collider records and the
+BVH's boxes are recomputed there from a resident copy of the rest pose (srt_pose_colliders, csrc/rt_pose.h),
+while the Python colliders below keep the rest pose.  `rotate()` still rewrites the Python colliders, which costs
+a full lowering and upload of the mesh.
 """
 import numpy as np
 
@@ -82,3 +87,68 @@ class TriangleMesh(Primitive):
             self.collider_list += [
                 Triangle_Collider(assigned_primitive=self, p1=p1, p2=p2, p3=p3, normals=normals, uvs=uvs)
             ]
+        # device posing (set_pose): the 12 numbers of the current pose or None, whether the mesh has ever been
+        # posed, the lowered records of its colliders (filled by _lower.lower_scene), and a counter of
+        # invalidate() calls (temporal motion: a mesh invalidated between two frames has no pose pair)
+        self._pose = None
+        self._device_posed = False
+        self._record_cache = None
+        self._epoch = 0
+
+    def set_pose(self, R, t=(0.0, 0.0, 0.0)):
+        """Pose the mesh rigidly on the device: a point x_rest of the mesh as it was loaded (or last rotate()d,
+        the rest pose) is rendered at R (x_rest - center) + center + t.  `R`: a 3 x 3 rotation (ValueError unless
+        R R^T = I within 1e-9 and det R > 0), `t`: three numbers.  Poses are absolute, not cumulative.
+
+        The Python colliders keep the rest pose: only the device's collider records and BVH boxes are
+        recomputed (srt_pose_colliders), from R and T = center - R center + t, computed here once in float64.
+        From the first call on the mesh is device-posed: the scene lowering takes its records from a cache
+        kept on the mesh, so a frame in which only poses changed lowers, hashes, builds and uploads nothing
+        for it.  Direct edits of a device-posed mesh's colliders (or of `center`) are therefore not seen until
+        invalidate() is called; rotate() calls it.  Scenes with user Collider / Material / texture / Light
+        subclasses and renders on several GPUs read the Python colliders and refuse a posed mesh
+        (NotImplementedError)."""
+        R = np.array(R, dtype=np.float64)
+        t = np.array(t, dtype=np.float64).reshape(-1)
+        if R.shape != (3, 3) or t.shape != (3,):
+            raise ValueError("set_pose: R must be 3 x 3 and t three numbers, not %r and %r" % (R.shape, t.shape))
+        if not (np.isfinite(R).all() and np.isfinite(t).all()):
+            raise ValueError("set_pose: R and t must be finite")
+        if np.abs(R @ R.T - np.eye(3)).max() > 1e-9 or np.linalg.det(R) <= 0.0:
+            raise ValueError("set_pose: R is not a rotation (R R^T = I within 1e-9 and det R > 0)")
+        c = np.array([self.center.x, self.center.y, self.center.z], dtype=np.float64)
+        self._pose = np.concatenate([R.reshape(-1), c - R @ c + t])
+        self._device_posed = True
+
+    def reset_pose(self):
+        """Back to the rest pose (the mesh stays device-posed: its records stay cached)."""
+        self._pose = None
+
+    @property
+    def pose(self):
+        """The 12 numbers handed to the device, R row-major then T, or None in the rest pose."""
+        return None if self._pose is None else self._pose.copy()
+
+    def invalidate(self):
+        """Drop the cached records after the colliders were edited: the next lowering reads them again."""
+        self._record_cache = None
+        self._epoch += 1
+
+    def rotate(self, θ, u):
+        super().rotate(θ, u)
+        self.invalidate()
+
+    def rest_vertices(self):
+        """(n, 3, 3) float64: p1, p2, p3 of every triangle as the Python colliders hold them."""
+        return np.array([[[p.x, p.y, p.z] for p in (c.p1, c.p2, c.p3)] for c in self.collider_list],
+                        dtype=np.float64).reshape(-1, 3, 3)
+
+    def posed_vertices(self):
+        """(n, 3, 3) float64: the vertices the device renders, x'_k = ((R[k][0] x + R[k][1] y) + R[k][2] z)
+        + T[k] in exactly this order (the rule of srt_pose_colliders); the rest vertices without a pose."""
+        V = self.rest_vertices()
+        if self._pose is None:
+            return V
+        R, T = self._pose[:9].reshape(3, 3), self._pose[9:]
+        x, y, z = V[..., 0], V[..., 1], V[..., 2]
+        return np.stack([((R[k, 0] * x + R[k, 1] * y) + R[k, 2] * z) + T[k] for k in range(3)], axis=-1)

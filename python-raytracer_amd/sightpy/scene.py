@@ -245,7 +245,8 @@ class Scene:
                 mt = []
                 rows = self._history.accumulate(A, Bh, aovs, B.camera_desc(self.camera), W, H,
                                                 demodulate=params["demodulate"], timings=mt, colliders=aovs["colliders"],
-                                                motion=motion, max_history=params["max_history"],
+                                                motion=motion, posed=aovs.get("posed", ()),
+                                                max_history=params["max_history"],
                                                 normal_max=params["temporal_normal"], plane_max=params["temporal_plane"])
                 extra["ms_temporal"] = mt[0]
                 if motion:
