@@ -38,6 +38,9 @@
  *                              scene.py:85)
  *   srt_pose_colliders:    no counterpart (a TriangleMesh moved rigidly on the device: its collider records
  *                             and the BVH's boxes recomputed from a resident copy of the rest pose)
+ *   srt_deform_topology, srt_deform_colliders: no counterpart (a TriangleMesh whose vertices change: its collider
+ *                             records, area-weighted vertex normals and the BVH's boxes recomputed on the device
+ *                             from a vertex array of 24 bytes per vertex)
  *
  * Conventions
  *   - Every entry point returns 0 on success or a negative SRT_ERR_* code; the message of the
@@ -380,6 +383,47 @@ int srt_upload_scene(srt_ctx* ctx, const srt_scene_desc* scene);
  * Triangle, overlapping ranges, a pose entry that is not finite. */
 int srt_pose_colliders(srt_ctx* ctx, int32_t n_ranges, const int32_t* first, const int32_t* count,
                        const double* poses /* [n_ranges][12] */);
+/* srt_deform_topology: no counterpart.  Register the indexed form of a triangle mesh of the resident scene, once
+ * per mesh and scene upload (the next srt_upload_scene drops every registration), for srt_deform_colliders.
+ *   first, count   the mesh's colliders [first, first + count), one Triangle per face
+ *   n_verts        vertices of the mesh
+ *   corners        [count][3] vertex indices of the faces' corners p1, p2, p3
+ *   center         3 doubles: vertex i of an array P is rendered at P[i] + center, componentwise
+ *   recompute      [count][3] bytes, nonzero: the corner's normal is the area-weighted vertex normal, recomputed by
+ *                  every srt_deform_colliders (SRT_CF_VNORMAL colliders only); zero: it stays what was uploaded
+ * The library keeps on the device the corner table, the flags and, per vertex, the corners naming it as a CSR list
+ * in ascending face order.  Every index is checked here, on the host: the kernels see none that was not.
+ * SRT_ERR_ARG: no scene resident, a range outside the table or with count < 1 or covering a collider that is no
+ * Triangle, a range overlapping a registered one, n_verts < 1, a corner index outside [0, n_verts), a center that
+ * is not finite. */
+int srt_deform_topology(srt_ctx* ctx, int32_t first, int32_t count, int32_t n_verts, const int32_t* corners /* [count][3] */,
+                        const double* center /* [3] */, const uint8_t* recompute /* [count][3] */);
+/* srt_deform_colliders: no counterpart (the reference changes a mesh's shape by rebuilding its Python colliders).
+ * Recompute the records of registered meshes from new vertex arrays on the device: verts[m] points to n_verts x 3
+ * doubles of the mesh registered as [first[m], first[m] + count[m]); several meshes per call, one BVH refit.
+ * Positions are absolute: calling twice with the same arrays changes nothing, and the vertices the scene was
+ * uploaded with give the uploaded records and the built BVH nodes back bit for bit.
+ *   vertex      p = P[i] + center
+ *   record      from p1, p2, p3 as sightpy's Triangle_Collider computes it (the rule of srt_pose_colliders:
+ *               centroid, normal, n31, n12, n23 and, with either attribute flag, d2 and d3); the uvs, type, flags,
+ *               material and the other integer fields are kept
+ *   normals     of corners registered with `recompute`: normalize(the sum, in ascending face order and once per
+ *               corner naming the vertex, of the unnormalised (P[b] - P[a]) x (P[c] - P[a]), without center), or
+ *               normalize(the new face normal) where that sum is exactly zero; other corners' normals are kept
+ *   tables      the records are written to the rest-pose copy and to the table the kernels read: the ranges return
+ *               to the identity pose (pose them again with srt_pose_colliders), and a later pose call sees the
+ *               deformed mesh as the rest shape
+ *   BVH         refitted as by srt_pose_colliders (the topology stays the uploaded scene's; a scene without a BVH
+ *               is deformed all the same); the traversal's bound (the f32 box test's widening constant) follows
+ *               from the largest |coordinate| of the triangles' vertices by that call's rule.  That holds after
+ *               the uploaded vertices too: records and nodes come back bit for bit, the bound does not -- it is
+ *               the rule's conservative value, a little above the build's largest |box coordinate|, and it stays
+ *               the rest shape's bound for later pose calls until the next upload.  Frames do not depend on it
+ * The call first waits for asynchronous frames in flight and returns after the device finished.  SRT_ERR_ARG: no
+ * scene resident, n_meshes < 1, a range that is not registered or named twice, a null vertex array, a coordinate
+ * that is not finite. */
+int srt_deform_colliders(srt_ctx* ctx, int32_t n_meshes, const int32_t* first, const int32_t* count,
+                         const double* const* verts /* [n_meshes] -> [n_verts][3] */);
 int srt_render(srt_ctx* ctx, const srt_camera* cam, const srt_render_args* args, srt_stats* stats);
 /* Queue the numpy-stream generation of the synchronous whole frame that srt_render will be called
  * for next with the same camera size and args (args->mt set, no rows, not SRT_RENDER_ASYNC /
@@ -713,6 +757,10 @@ int srt_debug_lean_launches(srt_ctx* ctx, int64_t* launches);
 /* Diagnostic: device time of the last srt_pose_colliders call by HIP events (ms: the record kernel, the
  * summed BVH refit launches) and the calls made since the context was created.  Any output may be NULL. */
 int srt_debug_pose_times(srt_ctx* ctx, double* ms_pose, double* ms_refit, int64_t* calls);
+/* Diagnostic: device time of the last srt_deform_colliders call by HIP events (ms: the face products and vertex
+ * sums, the record kernel, the summed BVH refit launches) and the calls made since the context was created.  Any
+ * output may be NULL. */
+int srt_debug_deform_times(srt_ctx* ctx, double* ms_normals, double* ms_records, double* ms_refit, int64_t* calls);
 const char* srt_last_error(void);
 
 #ifdef __cplusplus

@@ -15,6 +15,7 @@
 #include "rt_device.h"
 #include "rt_mt.h"
 #include "rt_pose.h"
+#include "rt_deform.h"
 
 using namespace rt;
 
@@ -609,6 +610,114 @@ int hc_pose_nearest(const srt_scene_desc* d, int n_ranges, const int32_t* first,
     SceneView S = view_of(d);
     std::vector<srt_collider> col(d->colliders, d->colliders + d->n_colliders);
     pose_and_refit(d, n_ranges, first, count, poses, col, g_bvh);
+    S.col = col.data();
+    S.bvh_bound = g_bvh.bound;
+    for (int64_t i = 0; i < n; ++i) {
+        double tn, on;
+        bool ties;
+        int c = nearest_hit(S, d3{O[i], O[n + i], O[2 * n + i]}, d3{D[i], D[n + i], D[2 * n + i]}, tn, on, ties);
+        if (t) t[i] = tn;
+        if (id) id[i] = c;
+        if (orient) orient[i] = on;
+    }
+    return SRT_OK;
+}
+
+// ---- deformed triangle meshes (rt_deform.h) ----
+namespace {
+// One mesh as srt_deform_topology registers it and srt_deform_colliders is handed it (host pointers).
+struct HcDeform {
+    int32_t first, count, n_verts;
+    const int32_t* corner;
+    const uint8_t* recompute;
+    const double* center;
+    const double* P;
+};
+// the three steps of srt_deform_colliders over rest[0, count) (the mesh's own records), in the kernels' order;
+// false for a corner index outside [0, n_verts) (which the library refuses at registration)
+bool deform_records(const HcDeform& h, const srt_collider* rest, srt_collider* out) {
+    for (int j = 0; j < 3 * h.count; ++j)
+        if (h.corner[j] < 0 || h.corner[j] >= h.n_verts) return false;
+    std::vector<int32_t> offset, list;
+    deform_csr(h.corner, h.count, h.n_verts, offset, list);
+    std::vector<double> cross((size_t)3 * h.count, 0.0), sum((size_t)3 * h.n_verts, 0.0);
+    DeformMesh M{};
+    M.first = h.first, M.count = h.count, M.n_verts = h.n_verts;
+    M.corner = h.corner, M.recompute = h.recompute, M.csr_offset = offset.data(), M.csr_corner = list.data();
+    for (int k = 0; k < 3; ++k) M.center[k] = h.center[k];
+    M.P = h.P, M.face_cross = cross.data(), M.vertex_sum = sum.data();
+    for (int f = 0; f < h.count; ++f) deform_face_cross(M, f);
+    for (int v = 0; v < h.n_verts; ++v) deform_vertex_sum(M, v);
+    for (int f = 0; f < h.count; ++f) {
+        srt_collider rec;
+        deform_triangle_record(M, f, rest[f], rec);
+        out[f] = rec;
+    }
+    return true;
+}
+// srt_deform_colliders on the host: the mesh's range of `col` rewritten, the built tree `B` refitted and its
+// bound recomputed as the library recomputes it
+bool deform_and_refit(const HcDeform& h, std::vector<srt_collider>& col, BvhBuild& B) {
+    if (h.first < 0 || h.count < 1 || (size_t)h.first + h.count > col.size()) return false;
+    std::vector<srt_collider> rest(col.begin() + h.first, col.begin() + h.first + h.count);
+    if (!deform_records(h, rest.data(), col.data() + h.first)) return false;
+    if (B.nodes.empty()) return true;
+    BvhLevels lv;
+    bvh_levels(B.nodes, lv);
+    for (size_t g = 0; g + 1 < lv.offset.size(); ++g)
+        for (int j = lv.offset[g]; j < lv.offset[g + 1]; ++j)
+            for (int k = 0; k < 4; ++k) bvh_refit_slot(B.nodes.data(), B.tri.data(), col.data(), lv.nodes[j], k);
+    B.bound = pose_bound(pose_static_reach(col.data(), (int)col.size(), std::vector<uint8_t>(col.size(), 0).data()));
+    return true;
+}
+}  // namespace
+
+// The records rest[0, count) of a mesh under the vertex array P, as k_deform_triangles writes them (0, or -1 for
+// a corner index outside [0, n_verts)).
+int hc_deform_triangles(const srt_collider* rest, int count, int n_verts, const int32_t* corner,
+                        const uint8_t* recompute, const double* center, const double* P, srt_collider* out) {
+    return deform_records(HcDeform{0, count, n_verts, corner, recompute, center, P}, rest, out) ? 0 : -1;
+}
+
+// hc_bvh_refit for a deformed mesh: `d`'s BVH as built, the mesh [first, first + count) deformed and the tree
+// refitted, then (n_ranges > 0) the ranges posed from the deformed table as srt_pose_colliders would after
+// srt_deform_colliders.  Outputs as hc_bvh_refit's; -1 for a bad range or corner index.
+int hc_deform_refit(const srt_scene_desc* d, int first, int count, int n_verts, const int32_t* corner,
+                    const uint8_t* recompute, const double* center, const double* P, int n_ranges,
+                    const int32_t* pfirst, const int32_t* pcount, const double* poses, void* nodes, int cap_nodes,
+                    int32_t* tri, int cap_tri, srt_collider* out, float* bound) {
+    BvhBuild B;
+    bvh_build(d->colliders, d->n_colliders, B);
+    std::vector<srt_collider> col(d->colliders, d->colliders + d->n_colliders);
+    if (!deform_and_refit(HcDeform{first, count, n_verts, corner, recompute, center, P}, col, B)) return -1;
+    if (n_ranges > 0) {
+        srt_scene_desc dd = *d;  // the deformed table is the rest shape of the pose
+        const std::vector<srt_collider> rest = col;
+        dd.colliders = rest.data();
+        pose_and_refit(&dd, n_ranges, pfirst, pcount, poses, col, B);
+    }
+    if (nodes && !B.nodes.empty())
+        memcpy(nodes, B.nodes.data(), sizeof(BvhNode) * (size_t)std::min<int>(cap_nodes, (int)B.nodes.size()));
+    if (tri && !B.tri.empty()) memcpy(tri, B.tri.data(), 4 * (size_t)std::min<int>(cap_tri, (int)B.tri.size()));
+    if (out && !col.empty()) memcpy(out, col.data(), sizeof(srt_collider) * col.size());
+    if (bound) *bound = B.bound;
+    return (int)B.nodes.size();
+}
+
+// hc_pose_nearest for a deformed (and then posed) mesh: through the refitted BVH, or (hc_set_bvh(0)) the linear loop
+int hc_deform_nearest(const srt_scene_desc* d, int first, int count, int n_verts, const int32_t* corner,
+                      const uint8_t* recompute, const double* center, const double* P, int n_ranges,
+                      const int32_t* pfirst, const int32_t* pcount, const double* poses, const double* O,
+                      const double* D, int64_t n, double* t, int32_t* id, double* orient) {
+    SceneView S = view_of(d);
+    std::vector<srt_collider> col(d->colliders, d->colliders + d->n_colliders);
+    if (!deform_and_refit(HcDeform{first, count, n_verts, corner, recompute, center, P}, col, g_bvh)) return -1;
+    if (n_ranges > 0) {
+        srt_scene_desc dd = *d;
+        const std::vector<srt_collider> rest = col;
+        dd.colliders = rest.data();
+        pose_and_refit(&dd, n_ranges, pfirst, pcount, poses, col, g_bvh);
+    }
     S.col = col.data();
     S.bvh_bound = g_bvh.bound;
     for (int64_t i = 0; i < n; ++i) {

@@ -8,8 +8,10 @@
 //   rt_aux_kernels.h    k_pass_end, k_resolve, the API kernels, k_assemble, k_rgbx, k_seed_queue, k_gather_children
 //   rt_devmem.h         DevBuf / DevList, dalloc, grid_for
 //   (rt_pose.h, with the headers above: pose_triangle_record, k_pose_triangles, k_bvh_refit)
+//   (rt_deform.h, likewise: deform_triangle_record, k_deform_face_cross / _vertex_normals / _triangles)
 //   (this file)         the context and its frame slots, the MT host side, frame collection and gather,
-//                       srt_create and the options, scene upload, srt_pose_colliders
+//                       srt_create and the options, scene upload, srt_pose_colliders,
+//                       srt_deform_topology and srt_deform_colliders
 //   rt_render.h         render_impl, before srt_render and its siblings
 //   rt_api_trace.h      trace_impl, srt_trace and srt_shade*
 //   rt_api_entry.h      the single-kernel entry points, AOVs and denoise, device memory, srt_mt19937_uniforms
@@ -61,6 +63,7 @@
 #include "rt_mt.h"
 #include "rt_mt_kernel.h"
 #include "rt_pose.h"
+#include "rt_deform.h"
 
 using namespace rt;
 using namespace rtmt_dev;
@@ -191,6 +194,19 @@ struct srt_ctx {
     hipEvent_t pose_ev[3] = {nullptr, nullptr, nullptr};  // start, after k_pose_triangles, after the refit
     double pose_ms[2] = {0.0, 0.0};                       // (srt_debug_pose_times) of the last call
     int64_t pose_calls = 0;
+    bool pose_active = false;                             // the last call left a range in another pose than the identity
+    // deformed triangle meshes (srt_deform_topology / srt_deform_colliders, rt_deform.h): the registered meshes,
+    // whose tables and vertex arrays are in scene_bufs (allocated after every table of the upload, released with
+    // them); `P` is DeformMesh::P for the copy in, `normals` whether any corner's normal is recomputed
+    struct DeformTopo {
+        DeformMesh m;
+        double* P = nullptr;
+        bool normals = false;
+    };
+    std::vector<DeformTopo> deform_meshes;
+    hipEvent_t deform_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // start, after the normals, the records, the refit
+    double deform_ms[3] = {0.0, 0.0, 0.0};                           // (srt_debug_deform_times) of the last call
+    int64_t deform_calls = 0;
     // texel pool (outside scene_bufs: survives re-uploads with the same texel_key)
     DevBuf<uint8_t> texels;
     uint64_t texel_key = 0;
@@ -1057,6 +1073,8 @@ srt_ctx::~srt_ctx() {
     if (mt_done) (void)hipEventDestroy(mt_done);
     for (hipEvent_t e : pose_ev)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : deform_ev)
+        if (e) (void)hipEventDestroy(e);
     if (mt_stream) (void)hipStreamDestroy(mt_stream);
 }
 
@@ -1473,6 +1491,8 @@ int srt_upload_scene(srt_ctx* c, const srt_scene_desc* d) {
     c->bvh_tri_dev = c->bvh_level_nodes = nullptr;
     c->bvh_level_offset.clear();
     c->pose_layout = srt_ctx::PoseLayout{};
+    c->pose_active = false;
+    c->deform_meshes.clear();
     SceneView S{};
     bool lin_tri = false;
     if ((rc = upload_tables(c, d, S, lin_tri))) return rc;
@@ -1557,6 +1577,7 @@ int srt_pose_colliders(srt_ctx* c, int32_t n_ranges, const int32_t* first, const
         }
         c->S.bvh_bound = all_identity ? c->bvh_bound_rest : pose_bound(reach);
     }
+    c->pose_active = !all_identity;
     HIP_TRY(hipEventRecord(c->pose_ev[2], st));
     HIP_TRY(hipStreamSynchronize(st));  // the next frame may run on another slot's stream
     float ms = 0.0f;
@@ -1573,6 +1594,139 @@ int srt_debug_pose_times(srt_ctx* c, double* ms_pose, double* ms_refit, int64_t*
     if (ms_pose) *ms_pose = c->pose_ms[0];
     if (ms_refit) *ms_refit = c->pose_ms[1];
     if (calls) *calls = c->pose_calls;
+    return SRT_OK;
+}
+
+// ---- srt_deform_topology, srt_deform_colliders ----
+int srt_deform_topology(srt_ctx* c, int32_t first, int32_t count, int32_t n_verts, const int32_t* corners,
+                        const double* center, const uint8_t* recompute) {
+    if (!c) return fail(SRT_ERR_ARG, "srt_deform_topology: null ctx");
+    if (!c->has_scene || !c->col_live || !c->col_rest) return fail(SRT_ERR_ARG, "srt_deform_topology: no scene is resident");
+    if (!corners || !center || !recompute) return fail(SRT_ERR_ARG, "srt_deform_topology: needs corners, center and the corner flags");
+    const int ncol = (int)c->col_host.size();
+    if (first < 0 || count < 1 || (int64_t)first + count > ncol)
+        return fail(SRT_ERR_ARG, "srt_deform_topology: the range lies outside the collider table");
+    for (int i = first; i < first + count; ++i)
+        if (c->col_host[i].type != SRT_TRIANGLE)
+            return fail(SRT_ERR_ARG, "srt_deform_topology: the range covers a collider that is no Triangle");
+    for (const srt_ctx::DeformTopo& t : c->deform_meshes)
+        if (first < t.m.first + t.m.count && t.m.first < first + count)
+            return fail(SRT_ERR_ARG, "srt_deform_topology: the range overlaps a registered one");
+    if (n_verts < 1) return fail(SRT_ERR_ARG, "srt_deform_topology: needs n_verts >= 1");
+    bool normals = false;
+    for (int64_t j = 0; j < 3 * (int64_t)count; ++j) {
+        if (corners[j] < 0 || corners[j] >= n_verts)
+            return fail(SRT_ERR_ARG, "srt_deform_topology: a corner index lies outside [0, n_verts)");
+        normals = normals || recompute[j];
+    }
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(center[k])) return fail(SRT_ERR_ARG, "srt_deform_topology: center is not finite");
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<int32_t> offset, list;
+    deform_csr(corners, count, n_verts, offset, list);
+    srt_ctx::DeformTopo t;
+    int32_t *d_corner, *d_offset, *d_list;
+    uint8_t* d_flag;
+    HIP_TRY(c->scene_bufs.in(&d_corner, corners, 3 * (int64_t)count));
+    HIP_TRY(c->scene_bufs.in(&d_flag, recompute, 3 * (int64_t)count));
+    HIP_TRY(c->scene_bufs.in(&d_offset, (const int32_t*)offset.data(), (int64_t)offset.size()));
+    HIP_TRY(c->scene_bufs.in(&d_list, (const int32_t*)list.data(), (int64_t)list.size()));
+    HIP_TRY(c->scene_bufs.alloc(&t.P, 3 * (int64_t)n_verts));
+    HIP_TRY(c->scene_bufs.alloc(&t.m.face_cross, 3 * (int64_t)count));
+    HIP_TRY(c->scene_bufs.alloc(&t.m.vertex_sum, 3 * (int64_t)n_verts));
+    t.m.first = first, t.m.count = count, t.m.n_verts = n_verts;
+    t.m.corner = d_corner, t.m.recompute = d_flag, t.m.csr_offset = d_offset, t.m.csr_corner = d_list;
+    t.m.P = t.P;
+    for (int k = 0; k < 3; ++k) t.m.center[k] = center[k];
+    t.normals = normals;
+    c->deform_meshes.push_back(t);
+    return SRT_OK;
+}
+
+int srt_deform_colliders(srt_ctx* c, int32_t n_meshes, const int32_t* first, const int32_t* count,
+                         const double* const* verts) {
+    if (!c) return fail(SRT_ERR_ARG, "srt_deform_colliders: null ctx");
+    if (!c->has_scene || !c->col_live || !c->col_rest) return fail(SRT_ERR_ARG, "srt_deform_colliders: no scene is resident");
+    if (n_meshes < 1 || !first || !count || !verts) return fail(SRT_ERR_ARG, "srt_deform_colliders: needs n_meshes >= 1 ranges and their vertex arrays");
+    std::vector<int> which((size_t)n_meshes, -1);
+    for (int r = 0; r < n_meshes; ++r) {
+        for (size_t k = 0; k < c->deform_meshes.size(); ++k)
+            if (c->deform_meshes[k].m.first == first[r] && c->deform_meshes[k].m.count == count[r]) which[r] = (int)k;
+        if (which[r] < 0) return fail(SRT_ERR_ARG, "srt_deform_colliders: a range is not registered (srt_deform_topology)");
+        for (int q = 0; q < r; ++q)
+            if (which[q] == which[r]) return fail(SRT_ERR_ARG, "srt_deform_colliders: a range is named twice");
+        if (!verts[r]) return fail(SRT_ERR_ARG, "srt_deform_colliders: a vertex array is null");
+        const int64_t n = 3 * (int64_t)c->deform_meshes[which[r]].m.n_verts;
+        for (int64_t j = 0; j < n; ++j)
+            if (!std::isfinite(verts[r][j])) return fail(SRT_ERR_ARG, "srt_deform_colliders: a coordinate is not finite");
+    }
+    int rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = finish_async(c, nullptr))) return rc;  // frames in flight read the tables rewritten below
+    const hipStream_t st = c->f->stream;
+    HIP_TRY(hipStreamSynchronize(st));
+    for (hipEvent_t& e : c->deform_ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    const int ncol = (int)c->col_host.size();
+    for (int r = 0; r < n_meshes; ++r) {
+        const srt_ctx::DeformTopo& t = c->deform_meshes[which[r]];
+        HIP_TRY(hipMemcpyAsync(t.P, verts[r], sizeof(double) * 3 * (size_t)t.m.n_verts, hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(hipEventRecord(c->deform_ev[0], st));
+    for (int r = 0; r < n_meshes; ++r) {
+        const srt_ctx::DeformTopo& t = c->deform_meshes[which[r]];
+        if (!t.normals) continue;
+        hipLaunchKernelGGL(k_deform_face_cross, dim3((unsigned)((t.m.count + 255) / 256)), dim3(256), 0, st, t.m);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_deform_vertex_normals, dim3((unsigned)((t.m.n_verts + 255) / 256)), dim3(256), 0, st, t.m);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(c->deform_ev[1], st));
+    for (int r = 0; r < n_meshes; ++r) {
+        const srt_ctx::DeformTopo& t = c->deform_meshes[which[r]];
+        hipLaunchKernelGGL(k_deform_triangles, dim3((unsigned)((t.m.count + 255) / 256)), dim3(256), 0, st, t.m,
+                           c->col_rest, c->col_live, ncol);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(c->deform_ev[2], st));
+    if (c->S.bvh_nodes > 0)
+        for (size_t h = 0; h + 1 < c->bvh_level_offset.size(); ++h) {
+            const int off = c->bvh_level_offset[h], n = c->bvh_level_offset[h + 1] - off;
+            if (n <= 0) continue;
+            hipLaunchKernelGGL(k_bvh_refit, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, st, c->bvh_dev,
+                               c->S.bvh_nodes, c->bvh_tri_dev, c->bvh_ntri, c->col_live, ncol, c->bvh_level_nodes + off, n);
+            HIP_TRY(hipGetLastError());
+        }
+    HIP_TRY(hipEventRecord(c->deform_ev[3], st));
+    // the host's copy of the rest table follows (a later pose call takes its boxes and reach from it)
+    for (int r = 0; r < n_meshes; ++r) {
+        const DeformMesh& m = c->deform_meshes[which[r]].m;
+        HIP_TRY(hipMemcpyAsync(c->col_host.data() + m.first, c->col_rest + m.first, sizeof(srt_collider) * (size_t)m.count,
+                               hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));  // the next frame may run on another slot's stream
+    c->pose_layout = srt_ctx::PoseLayout{};
+    if (c->S.bvh_nodes > 0) {
+        const float bound = pose_bound(pose_static_reach(c->col_host.data(), ncol, std::vector<uint8_t>((size_t)ncol, 0).data()));
+        // (ranges outside this call may still be posed: the bound that held for their boxes goes on holding)
+        c->S.bvh_bound = c->pose_active ? std::max(c->S.bvh_bound, bound) : bound;
+        c->bvh_bound_rest = bound;
+    }
+    float ms = 0.0f;
+    for (int k = 0; k < 3; ++k) {
+        HIP_TRY(hipEventElapsedTime(&ms, c->deform_ev[k], c->deform_ev[k + 1]));
+        c->deform_ms[k] = ms;
+    }
+    c->deform_calls++;
+    return SRT_OK;
+}
+
+int srt_debug_deform_times(srt_ctx* c, double* ms_normals, double* ms_records, double* ms_refit, int64_t* calls) {
+    if (!c) return fail(SRT_ERR_ARG, "null ctx");
+    if (ms_normals) *ms_normals = c->deform_ms[0];
+    if (ms_records) *ms_records = c->deform_ms[1];
+    if (ms_refit) *ms_refit = c->deform_ms[2];
+    if (calls) *calls = c->deform_calls;
     return SRT_OK;
 }
 

@@ -43,6 +43,33 @@ RT_HD void pose_put(double* p, d3 v) {
     p[2] = v.z;
 }
 
+// The fields of a triangle's record that follow from its three vertices alone, as Triangle_Collider computes
+// them, written to the record's parameters `p` in two steps (shared with the deformed meshes of rt_deform.h; every
+// other slot of `p` stays as it is): centroid, normal, the vertices, n31, n12, n23 ...
+struct TriangleEdges {
+    d3 n31, n12;
+};
+RT_HD TriangleEdges triangle_record_geometry(d3 p1, d3 p2, d3 p3, double* p) {
+    const d3 nrm = normalize(pose_cross(sub(p2, p1), sub(p3, p1)));
+    const d3 n31 = pose_cross(sub(p3, p1), nrm), n12 = pose_cross(sub(p1, p2), nrm);
+    pose_put(p + 0, divs(add(add(p1, p2), p3), 3.0));
+    pose_put(p + 3, nrm);
+    pose_put(p + 6, p1);
+    pose_put(p + 9, p2);
+    pose_put(p + 12, p3);
+    pose_put(p + 15, n31);
+    pose_put(p + 18, n12);
+    pose_put(p + 21, pose_cross(sub(p2, p3), nrm));
+    return TriangleEdges{n31, n12};
+}
+// ... and, with an attribute flag among `flags`, d2 and d3 (the uvs p[33..38] stay as copied)
+RT_HD void triangle_record_bary(uint32_t flags, TriangleEdges e, d3 p1, d3 p2, d3 p3, double* p) {
+    if (flags & (SRT_CF_VNORMAL | SRT_CF_VUV)) {
+        p[39] = dot(e.n31, sub(p2, p1));
+        p[40] = dot(e.n12, sub(p3, p2));
+    }
+}
+
 // The record of triangle `rest` under `pose` (type, flags, material and the other integer fields copied).
 template <class P>
 RT_HD void pose_triangle_record(const srt_collider& rest, P pose, srt_collider& out) {
@@ -52,23 +79,11 @@ RT_HD void pose_triangle_record(const srt_collider& rest, P pose, srt_collider& 
     const d3 p1 = pose_point(pose, d3{q[6], q[7], q[8]});
     const d3 p2 = pose_point(pose, d3{q[9], q[10], q[11]});
     const d3 p3 = pose_point(pose, d3{q[12], q[13], q[14]});
-    const d3 nrm = normalize(pose_cross(sub(p2, p1), sub(p3, p1)));
-    const d3 n31 = pose_cross(sub(p3, p1), nrm), n12 = pose_cross(sub(p1, p2), nrm);
-    pose_put(out.p + 0, divs(add(add(p1, p2), p3), 3.0));
-    pose_put(out.p + 3, nrm);
-    pose_put(out.p + 6, p1);
-    pose_put(out.p + 9, p2);
-    pose_put(out.p + 12, p3);
-    pose_put(out.p + 15, n31);
-    pose_put(out.p + 18, n12);
-    pose_put(out.p + 21, pose_cross(sub(p2, p3), nrm));
+    const TriangleEdges e = triangle_record_geometry(p1, p2, p3, out.p);
     if (rest.flags & SRT_CF_VNORMAL)
         for (int i = 0; i < 3; ++i)
             pose_put(out.p + 24 + 3 * i, normalize(pose_rotate(pose, d3{q[24 + 3 * i], q[25 + 3 * i], q[26 + 3 * i]})));
-    if (rest.flags & (SRT_CF_VNORMAL | SRT_CF_VUV)) {  // (the uvs p[33..38] stay as copied)
-        out.p[39] = dot(n31, sub(p2, p1));
-        out.p[40] = dot(n12, sub(p3, p2));
-    }
+    triangle_record_bary(rest.flags, e, p1, p2, p3, out.p);
 }
 
 // One slot of a BVH node from what lies below it: a leaf slot's box is the union of its triangles' boxes

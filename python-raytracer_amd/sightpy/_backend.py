@@ -18,6 +18,10 @@ _STATE = {"lib": None, "ctx": None, "device": None, "scene_sig": {}, "scene_inpu
 # device-posed meshes (TriangleMesh.set_pose): the poses resident per context, and how often upload() called
 # srt_upload_scene and srt_pose_colliders
 _STATE.update({"pose_sig": {}, "uploads": 0, "pose_calls": 0})
+# device-deformed meshes (TriangleMesh.set_vertices): per context, the vertex version resident for each mesh range
+# that is not in its loaded shape ({(first, count): (mesh key, version)}) and the ranges whose topology is
+# registered since the last upload; how often upload() called srt_deform_colliders
+_STATE.update({"vert_sig": {}, "deform_topology": {}, "deform_calls": 0})
 
 
 class RenderResult:
@@ -121,11 +125,22 @@ def _pose_sig(posed, identity=False):
     return tuple((p["first"], p["count"], (POSE_IDENTITY if identity else p["pose"]).tobytes()) for p in posed)
 
 
+def _vert_version(p):
+    """The vertex array a Lowered.posed entry wants resident, as a comparable value; None: the loaded shape."""
+    return None if p.get("deform") is None else (p["key"], p["vver"])
+
+
 def upload(scene, extra_media=(), force=False, ctx=None):
     """Lower and upload `scene` to `ctx` (default: the process context) unless the identical tables
     are already resident there.  The poses of device-posed meshes (TriangleMesh.set_pose) are no part of the
     tables and are compared on their own: when only they changed, srt_pose_colliders alone is called
-    (_STATE["uploads"] and _STATE["pose_calls"] count the two kinds of call)."""
+    (_STATE["uploads"] and _STATE["pose_calls"] count the two kinds of call).  Neither are the vertex arrays of
+    deformed meshes (TriangleMesh.set_vertices): when the version resident for a mesh is not the one wanted,
+    srt_deform_colliders is called for those meshes (their topology registered first, once per upload), which
+    leaves them in the identity pose, so srt_pose_colliders follows if any pose is another
+    (_STATE["deform_calls"]).  Whenever a deformed range is resident that no deformed mesh of `scene` claims -- the
+    mesh went back to its loaded shape by invalidate(), or `scene` is another scene with the same tables -- the
+    scene is uploaded, although its signature is the resident one."""
     lib = library()
     if ctx is None:
         ctx = context()[1]
@@ -136,17 +151,54 @@ def upload(scene, extra_media=(), force=False, ctx=None):
     if want != _pose_sig(L.posed, identity=True) and len(devices()) > 1:
         raise NotImplementedError("a posed TriangleMesh (set_pose) renders on one GPU; %d are selected "
                                   "($SIGHTPY_DEVICES)" % len(devices()))
+    if any(p.get("deform") is not None for p in L.posed) and len(devices()) > 1:
+        raise NotImplementedError("a deformed TriangleMesh (set_vertices) renders on one GPU; %d are selected "
+                                  "($SIGHTPY_DEVICES)" % len(devices()))
+    # a deformed range resident that no deformed mesh of this scene claims: the tables are another shape's than the
+    # signature says (the mesh went back to its loaded shape without an array to restore it from -- invalidate() --
+    # or this is another scene with the same tables, a fresh Scene of the same OBJ for one): only an upload restores it
+    resident = _STATE["vert_sig"].get(key, {})
+    if set(resident) - {(p["first"], p["count"]) for p in L.posed if p.get("deform") is not None}:
+        force = True
     if force or sig != _STATE["scene_sig"].get(key):
         _STATE["scene_sig"].pop(key, None)
         _STATE["pose_sig"].pop(key, None)
+        _STATE["vert_sig"].pop(key, None)
+        _STATE["deform_topology"].pop(key, None)
         N.check(lib, lib.srt_upload_scene(ctx, ctypes.byref(L.desc())))
         _STATE["uploads"] += 1
         _STATE["scene_sig"][key] = sig
         _STATE["pose_sig"][key] = _pose_sig(L.posed, identity=True)  # (an upload leaves every mesh in its rest pose)
+        _STATE["vert_sig"][key] = {}                                 # (... and at its loaded vertices)
+        _STATE["deform_topology"][key] = set()
         # a scene shaded with per-hit inputs (a user texture / Light, _hybrid.py): the library refuses
         # every whole-frame entry point on it, srt_render_prefetch included
         _STATE["scene_inputs"][key] = bool((L.materials["flags"] & N.MF_HIT_ALBEDO).any()
                                            or (L.lights["type"] == N.LIGHT_USER).any())
+    resident = _STATE["vert_sig"].setdefault(key, {})
+    changed = [p for p in L.posed if p.get("deform") is not None and resident.get((p["first"], p["count"])) != _vert_version(p)]
+    if changed:
+        registered = _STATE["deform_topology"].setdefault(key, set())
+        for p in changed:
+            rng, d = (p["first"], p["count"]), p["deform"]
+            resident.pop(rng, None)
+            if rng not in registered:
+                corners = np.ascontiguousarray(d["corners"], dtype=np.int32)
+                flags = np.ascontiguousarray(d["recompute"], dtype=np.uint8)
+                center = np.ascontiguousarray(d["center"], dtype=np.float64)
+                N.check(lib, lib.srt_deform_topology(ctx, rng[0], rng[1], len(d["verts"]), N.ptr(corners), N.ptr(center),
+                                                     N.ptr(flags)))
+                registered.add(rng)
+        first = np.array([p["first"] for p in changed], dtype=np.int32)
+        count = np.array([p["count"] for p in changed], dtype=np.int32)
+        verts = [np.ascontiguousarray(p["deform"]["verts"], dtype=np.float64) for p in changed]
+        ptrs = (ctypes.c_void_p * len(verts))(*[N.ptr(v) for v in verts])
+        N.check(lib, lib.srt_deform_colliders(ctx, len(first), N.ptr(first), N.ptr(count), ptrs))
+        _STATE["deform_calls"] += 1
+        for p in changed:
+            resident[(p["first"], p["count"])] = _vert_version(p)
+        if want != _pose_sig(L.posed, identity=True):
+            _STATE["pose_sig"].pop(key, None)  # (the deformed ranges are back in the identity pose)
     if want != _STATE["pose_sig"].get(key, ()):
         _STATE["pose_sig"].pop(key, None)
         first = np.array([p["first"] for p in L.posed], dtype=np.int32)
@@ -984,7 +1036,7 @@ class TemporalHistory:
                             out={"a": rgb_a, "b": rgb_b, "hist_a": nxt["a"], "hist_b": nxt["b"], "len": nxt["len"]},
                             motion=table, **params)
         self.prev_colliders = np.array(colliders, copy=True) if motion else None
-        self.prev_posed = [dict(p, pose=p["pose"].copy()) for p in posed] if motion else []
+        self.prev_posed = [dict(p, pose=p["pose"].copy(), deform=None) for p in posed] if motion else []
         for k, bytes_pp in self.PLANES[3:]:  # this frame's guides are the next frame's history guides
             N.check(lib, lib.srt_memcpy(ctx, nxt[k], _addr(aovs[k]), bytes_pp * n))
         cam = N.CameraDesc()

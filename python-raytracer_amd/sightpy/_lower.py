@@ -72,7 +72,11 @@ class Lowered:
         # device-posed meshes (TriangleMesh.set_pose): one dict per mesh, "first" / "count" (its range of device
         # collider indices), "pose" (12 float64, R row-major then T; the identity in the rest pose) and "key"
         # ((id(mesh), its invalidate() count): equal keys in two frames name the same rest geometry).  The
-        # collider table holds such a mesh in its rest pose; the poses are no part of signature()
+        # collider table holds such a mesh in its rest pose; the poses are no part of signature().  For a mesh
+        # deformed on the device (TriangleMesh.set_vertices) also "deform": None in the loaded shape, else a dict
+        # of "corners" (n_f, 3) int32, "recompute" (n_f, 3) uint8, "center" (3,) float64 and "verts" (n_v, 3)
+        # float64, what srt_deform_topology and srt_deform_colliders take; and "vver", the mesh's count of vertex
+        # arrays set.  The table holds the loaded shape; the vertices are no part of signature() either
         self.posed = []
 
     def light_table(self):
@@ -539,6 +543,10 @@ def lower_scene(scene, extra_media=()):
                 raise NotImplementedError(
                     "a posed TriangleMesh (set_pose) in a scene with user Collider / Material / texture / Light "
                     "subclasses: that path reads the Python colliders, which keep the rest pose")
+            if hybrid and prim._verts_cur is not None:
+                raise NotImplementedError(
+                    "a deformed TriangleMesh (set_vertices) in a scene with user Collider / Material / texture / "
+                    "Light subclasses: that path reads the Python colliders, which keep the loaded shape")
             recs = _mesh_records(prim)
             m = prim.material
             vuv = bool((recs["flags"] & N.CF_VUV).all())
@@ -556,8 +564,13 @@ def lower_scene(scene, extra_media=()):
             crecs["max_ray_depth"][i:i + span] = int(prim.max_ray_depth)
             crecs["flags"][i:i + span] |= flags
             crecs["primitive"][i:i + span] = prim_index.setdefault(id(prim), len(prim_index))
+            deform = None
+            if prim._verts_cur is not None:
+                deform = {"corners": prim._corners, "recompute": prim._recompute, "verts": prim._verts_cur.copy(),
+                          "center": np.array([prim.center.x, prim.center.y, prim.center.z], dtype=np.float64)}
             L.posed.append({"first": i, "count": span, "key": (id(prim), prim._epoch),
-                            "pose": POSE_IDENTITY.copy() if prim._pose is None else prim._pose.copy()})
+                            "pose": POSE_IDENTITY.copy() if prim._pose is None else prim._pose.copy(),
+                            "deform": deform, "vver": prim._vert_version})
             skip_to = i + span
             continue
         rec = collider_record(c)

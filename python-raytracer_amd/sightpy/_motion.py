@@ -89,12 +89,15 @@ def pose_motion(rows, prev_posed, cur_posed):
     point x of the current frame was at R_prev R_cur^T (x - T_cur) + T_prev (R_cur is a rotation: its inverse
     is its transpose), the same row for every collider of the mesh -- the records are not looked at.  Equal
     poses give the identity row exactly.  A mesh without an entry of the same key and range in `prev_posed`
-    (first posed in this frame, invalidated or moved in the list since) gets NaN rows."""
+    (first posed in this frame, invalidated or moved in the list since) gets NaN rows, and so does a mesh whose
+    vertex version ("vver", read with .get: TriangleMesh.set_vertices) differs between the two frames: its shape
+    changed, no rigid row describes that, and it has no history."""
     prev = {p["key"]: p for p in prev_posed}
     for cur in cur_posed:
         sl = slice(cur["first"], cur["first"] + cur["count"])
         old = prev.get(cur["key"])
-        if old is None or (old["first"], old["count"]) != (cur["first"], cur["count"]):
+        if (old is None or (old["first"], old["count"]) != (cur["first"], cur["count"])
+                or old.get("vver") != cur.get("vver")):
             rows[sl] = np.nan
         elif np.array_equal(old["pose"], cur["pose"]):
             rows[sl] = IDENTITY

@@ -361,6 +361,8 @@ SIGNATURES = {
     "srt_set_option": (ctypes.c_int, [_p, ctypes.c_char_p, ctypes.c_int64]),
     "srt_upload_scene": (ctypes.c_int, [_p, ctypes.POINTER(SceneDesc)]),
     "srt_pose_colliders": (ctypes.c_int, [_p, ctypes.c_int32, _p, _p, _p]),
+    "srt_deform_topology": (ctypes.c_int, [_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _p, _p, _p]),
+    "srt_deform_colliders": (ctypes.c_int, [_p, ctypes.c_int32, _p, _p, _p]),
     "srt_render": (ctypes.c_int, [_p, ctypes.POINTER(CameraDesc), ctypes.POINTER(RenderArgs), ctypes.POINTER(Stats)]),
     "srt_trace": (ctypes.c_int, [_p, ctypes.POINTER(TraceArgs), ctypes.POINTER(Stats)]),
     "srt_nearest": (ctypes.c_int, [_p, _p, _p, ctypes.c_int64, _p, _p, _p]),
@@ -389,6 +391,7 @@ SIGNATURES = {
     "srt_debug_lean_launches": (ctypes.c_int, [_p, ctypes.POINTER(ctypes.c_int64)]),
     "srt_debug_pose_times": (ctypes.c_int, [_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                             ctypes.POINTER(ctypes.c_int64)]),
+    "srt_debug_deform_times": (ctypes.c_int, [_p] + [ctypes.POINTER(ctypes.c_double)] * 3 + [ctypes.POINTER(ctypes.c_int64)]),
     "srt_render_prefetch": (ctypes.c_int, [_p, ctypes.POINTER(CameraDesc), ctypes.POINTER(RenderArgs)]),
     "srt_render_finish": (ctypes.c_int, [_p, ctypes.POINTER(Stats)]),
     "srt_stream": (ctypes.c_int, [_p, ctypes.POINTER(_p)]),
