@@ -1,5 +1,5 @@
 // rt_deform.h -- deformed triangle meshes: the collider records of a mesh, and the area-weighted vertex normals
-// of a smooth one, recomputed on the device from a new vertex array (srt_deform_colliders in rt_kernels.hip; the
+// of a smooth one, recomputed on the device from a new vertex array (srt_deform_colliders in rt_api_anim.h; the
 // CPU check harness rt_hostcheck.cpp runs the same functions).  The BVH's boxes are then refitted by rt_pose.h's
 // k_bvh_refit, and the trace kernels read the rewritten tables as they read uploaded ones.
 //

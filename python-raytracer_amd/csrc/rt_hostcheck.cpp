@@ -284,9 +284,9 @@ int hc_trace(const srt_scene_desc* d, const srt_trace_args* a, srt_stats* st) {
     return SRT_OK;
 }
 
-int hc_nearest(const srt_scene_desc* d, const double* O, const double* D, int64_t n, double* t, int32_t* id,
-               double* orient) {
-    SceneView S = view_of(d);
+// the nearest hit of each of the n rays (O, D: three planes of n) in `S`; each output may be NULL
+static int nearest_all(const SceneView& S, const double* O, const double* D, int64_t n, double* t, int32_t* id,
+                       double* orient) {
     for (int64_t i = 0; i < n; ++i) {
         double tn, on;
         bool ties;
@@ -296,6 +296,11 @@ int hc_nearest(const srt_scene_desc* d, const double* O, const double* D, int64_
         if (orient) orient[i] = on;
     }
     return SRT_OK;
+}
+
+int hc_nearest(const srt_scene_desc* d, const double* O, const double* D, int64_t n, double* t, int32_t* id,
+               double* orient) {
+    return nearest_all(view_of(d), O, D, n, t, id, orient);
 }
 
 int hc_intersect_collider(const srt_collider* c, const double* O, const double* D, int64_t n, double* out) {
@@ -555,76 +560,33 @@ void hc_pose_triangles(const srt_collider* rec, int n, const double* pose, srt_c
 }
 
 namespace {
-// srt_pose_colliders on the host: `col` (the scene's table, a copy) posed range by range, then the built
-// tree `B` refitted height by height and its bound recomputed as the library recomputes it
-void pose_and_refit(const srt_scene_desc* d, int n_ranges, const int32_t* first, const int32_t* count,
-                    const double* poses, std::vector<srt_collider>& col, BvhBuild& B) {
-    std::vector<uint8_t> posed(col.size(), 0);
-    double reach = 0.0;
-    bool all_identity = true;
-    for (int r = 0; r < n_ranges; ++r) {
-        const double* pose = poses + (size_t)r * POSE_DOUBLES;
-        double box[6];
-        pose_range_box(d->colliders, first[r], count[r], box);
-        reach = std::max(reach, pose_box_reach(box, box + 3, pose));
-        all_identity = all_identity && pose_is_identity(pose);
-        for (int i = first[r]; i < first[r] + count[r]; ++i) {
-            pose_triangle_record(d->colliders[i], pose, col[i]);
-            posed[i] = 1;
-        }
-    }
-    if (B.nodes.empty()) return;
+// the boxes of the built tree `B` over the table `col` as it stands, height by height (k_bvh_refit's launches)
+void refit_levels(BvhBuild& B, const srt_collider* col) {
     BvhLevels lv;
     bvh_levels(B.nodes, lv);
     for (size_t h = 0; h + 1 < lv.offset.size(); ++h)
         for (int j = lv.offset[h]; j < lv.offset[h + 1]; ++j)
-            for (int k = 0; k < 4; ++k) bvh_refit_slot(B.nodes.data(), B.tri.data(), col.data(), lv.nodes[j], k);
-    if (!all_identity)
-        B.bound = pose_bound(std::max(reach, pose_static_reach(d->colliders, d->n_colliders, posed.data())));
-}
-}  // namespace
-
-// The 4-wide nodes of `d`'s BVH after srt_pose_colliders' two steps on the host (n_ranges 0: as built).
-// Returns the node count; up to cap_nodes nodes (128 bytes each, rt_device.h BvhNode) go to `nodes`, up to
-// cap_tri leaf slots (collider indices) to `tri`, the posed table (d->n_colliders records) to `posed`, the
-// traversal's bound to `bound`; each may be NULL.
-int hc_bvh_refit(const srt_scene_desc* d, int n_ranges, const int32_t* first, const int32_t* count,
-                 const double* poses, void* nodes, int cap_nodes, int32_t* tri, int cap_tri, srt_collider* posed,
-                 float* bound) {
-    BvhBuild B;
-    bvh_build(d->colliders, d->n_colliders, B);
-    std::vector<srt_collider> col(d->colliders, d->colliders + d->n_colliders);
-    if (n_ranges > 0) pose_and_refit(d, n_ranges, first, count, poses, col, B);
-    if (nodes && !B.nodes.empty())
-        memcpy(nodes, B.nodes.data(), sizeof(BvhNode) * (size_t)std::min<int>(cap_nodes, (int)B.nodes.size()));
-    if (tri && !B.tri.empty()) memcpy(tri, B.tri.data(), 4 * (size_t)std::min<int>(cap_tri, (int)B.tri.size()));
-    if (posed && !col.empty()) memcpy(posed, col.data(), sizeof(srt_collider) * col.size());
-    if (bound) *bound = B.bound;
-    return (int)B.nodes.size();
+            for (int k = 0; k < 4; ++k) bvh_refit_slot(B.nodes.data(), B.tri.data(), col, lv.nodes[j], k);
 }
 
-// hc_nearest on the posed scene: through the refitted BVH, or (hc_set_bvh(0)) the linear loop over the posed table
-int hc_pose_nearest(const srt_scene_desc* d, int n_ranges, const int32_t* first, const int32_t* count,
-                    const double* poses, const double* O, const double* D, int64_t n, double* t, int32_t* id,
-                    double* orient) {
-    SceneView S = view_of(d);
-    std::vector<srt_collider> col(d->colliders, d->colliders + d->n_colliders);
-    pose_and_refit(d, n_ranges, first, count, poses, col, g_bvh);
-    S.col = col.data();
-    S.bvh_bound = g_bvh.bound;
-    for (int64_t i = 0; i < n; ++i) {
-        double tn, on;
-        bool ties;
-        int c = nearest_hit(S, d3{O[i], O[n + i], O[2 * n + i]}, d3{D[i], D[n + i], D[2 * n + i]}, tn, on, ties);
-        if (t) t[i] = tn;
-        if (id) id[i] = c;
-        if (orient) orient[i] = on;
-    }
-    return SRT_OK;
+// srt_pose_colliders on the host: the table `col` as it stands is the rest shape; it is posed range by range, then
+// the built tree `B` refitted and its bound set by the library's own rule (rt_pose.h); false for ranges the
+// library refuses
+bool pose_and_refit(int n_ranges, const int32_t* first, const int32_t* count, const double* poses,
+                    std::vector<srt_collider>& col, BvhBuild& B) {
+    const std::vector<srt_collider> rest = col;
+    PoseLayout PL;
+    if (!pose_layout_build(rest.data(), (int)rest.size(), n_ranges, first, count, PL).empty()) return false;
+    for (int r = 0; r < n_ranges; ++r)
+        for (int i = first[r]; i < first[r] + count[r]; ++i)
+            pose_triangle_record(rest[i], poses + (size_t)r * POSE_DOUBLES, col[i]);
+    if (B.nodes.empty()) return true;
+    refit_levels(B, col.data());
+    bool all_identity;
+    B.bound = pose_layout_bound(PL, poses, B.bound, all_identity);
+    return true;
 }
 
-// ---- deformed triangle meshes (rt_deform.h) ----
-namespace {
 // One mesh as srt_deform_topology registers it and srt_deform_colliders is handed it (host pointers).
 struct HcDeform {
     int32_t first, count, n_verts;
@@ -656,22 +618,74 @@ bool deform_records(const HcDeform& h, const srt_collider* rest, srt_collider* o
     return true;
 }
 // srt_deform_colliders on the host: the mesh's range of `col` rewritten, the built tree `B` refitted and its
-// bound recomputed as the library recomputes it
+// bound set by the library's own rule (rt_pose.h)
 bool deform_and_refit(const HcDeform& h, std::vector<srt_collider>& col, BvhBuild& B) {
     if (h.first < 0 || h.count < 1 || (size_t)h.first + h.count > col.size()) return false;
     std::vector<srt_collider> rest(col.begin() + h.first, col.begin() + h.first + h.count);
     if (!deform_records(h, rest.data(), col.data() + h.first)) return false;
     if (B.nodes.empty()) return true;
-    BvhLevels lv;
-    bvh_levels(B.nodes, lv);
-    for (size_t g = 0; g + 1 < lv.offset.size(); ++g)
-        for (int j = lv.offset[g]; j < lv.offset[g + 1]; ++j)
-            for (int k = 0; k < 4; ++k) bvh_refit_slot(B.nodes.data(), B.tri.data(), col.data(), lv.nodes[j], k);
-    B.bound = pose_bound(pose_static_reach(col.data(), (int)col.size(), std::vector<uint8_t>(col.size(), 0).data()));
+    refit_levels(B, col.data());
+    B.bound = rest_table_bound(col.data(), (int)col.size());
     return true;
+}
+
+// `d`'s table and tree `B` (as built) after an optional deformation (`h`, null: none) and then the poses of
+// n_ranges ranges (0: none), as srt_pose_colliders would follow srt_deform_colliders
+bool animate(const srt_scene_desc* d, const HcDeform* h, int n_ranges, const int32_t* first, const int32_t* count,
+             const double* poses, std::vector<srt_collider>& col, BvhBuild& B) {
+    col.assign(d->colliders, d->colliders + d->n_colliders);
+    if (h && !deform_and_refit(*h, col, B)) return false;
+    return n_ranges <= 0 || pose_and_refit(n_ranges, first, count, poses, col, B);
+}
+
+// hc_bvh_refit's and hc_deform_refit's outputs: the node count, or -1 for what the library refuses
+int refit_out(const srt_scene_desc* d, const HcDeform* h, int n_ranges, const int32_t* first, const int32_t* count,
+              const double* poses, void* nodes, int cap_nodes, int32_t* tri, int cap_tri, srt_collider* out,
+              float* bound) {
+    BvhBuild B;
+    bvh_build(d->colliders, d->n_colliders, B);
+    std::vector<srt_collider> col;
+    if (!animate(d, h, n_ranges, first, count, poses, col, B)) return -1;
+    if (nodes && !B.nodes.empty())
+        memcpy(nodes, B.nodes.data(), sizeof(BvhNode) * (size_t)std::min<int>(cap_nodes, (int)B.nodes.size()));
+    if (tri && !B.tri.empty()) memcpy(tri, B.tri.data(), 4 * (size_t)std::min<int>(cap_tri, (int)B.tri.size()));
+    if (out && !col.empty()) memcpy(out, col.data(), sizeof(srt_collider) * col.size());
+    if (bound) *bound = B.bound;
+    return (int)B.nodes.size();
+}
+
+// hc_pose_nearest's and hc_deform_nearest's: hc_nearest on the animated scene, through the refitted BVH or
+// (hc_set_bvh(0)) the linear loop over the rewritten table
+int nearest_out(const srt_scene_desc* d, const HcDeform* h, int n_ranges, const int32_t* first, const int32_t* count,
+                const double* poses, const double* O, const double* D, int64_t n, double* t, int32_t* id,
+                double* orient) {
+    SceneView S = view_of(d);
+    std::vector<srt_collider> col;
+    if (!animate(d, h, n_ranges, first, count, poses, col, g_bvh)) return -1;
+    S.col = col.data();
+    S.bvh_bound = g_bvh.bound;
+    return nearest_all(S, O, D, n, t, id, orient);
 }
 }  // namespace
 
+// The 4-wide nodes of `d`'s BVH after srt_pose_colliders' two steps on the host (n_ranges 0: as built).
+// Returns the node count (-1 for ranges the library refuses); up to cap_nodes nodes (128 bytes each, rt_device.h
+// BvhNode) go to `nodes`, up to cap_tri leaf slots (collider indices) to `tri`, the posed table (d->n_colliders
+// records) to `posed`, the traversal's bound to `bound`; each may be NULL.
+int hc_bvh_refit(const srt_scene_desc* d, int n_ranges, const int32_t* first, const int32_t* count,
+                 const double* poses, void* nodes, int cap_nodes, int32_t* tri, int cap_tri, srt_collider* posed,
+                 float* bound) {
+    return refit_out(d, nullptr, n_ranges, first, count, poses, nodes, cap_nodes, tri, cap_tri, posed, bound);
+}
+
+// hc_nearest on the posed scene
+int hc_pose_nearest(const srt_scene_desc* d, int n_ranges, const int32_t* first, const int32_t* count,
+                    const double* poses, const double* O, const double* D, int64_t n, double* t, int32_t* id,
+                    double* orient) {
+    return nearest_out(d, nullptr, n_ranges, first, count, poses, O, D, n, t, id, orient);
+}
+
+// ---- deformed triangle meshes (rt_deform.h) ----
 // The records rest[0, count) of a mesh under the vertex array P, as k_deform_triangles writes them (0, or -1 for
 // a corner index outside [0, n_verts)).
 int hc_deform_triangles(const srt_collider* rest, int count, int n_verts, const int32_t* corner,
@@ -686,49 +700,17 @@ int hc_deform_refit(const srt_scene_desc* d, int first, int count, int n_verts, 
                     const uint8_t* recompute, const double* center, const double* P, int n_ranges,
                     const int32_t* pfirst, const int32_t* pcount, const double* poses, void* nodes, int cap_nodes,
                     int32_t* tri, int cap_tri, srt_collider* out, float* bound) {
-    BvhBuild B;
-    bvh_build(d->colliders, d->n_colliders, B);
-    std::vector<srt_collider> col(d->colliders, d->colliders + d->n_colliders);
-    if (!deform_and_refit(HcDeform{first, count, n_verts, corner, recompute, center, P}, col, B)) return -1;
-    if (n_ranges > 0) {
-        srt_scene_desc dd = *d;  // the deformed table is the rest shape of the pose
-        const std::vector<srt_collider> rest = col;
-        dd.colliders = rest.data();
-        pose_and_refit(&dd, n_ranges, pfirst, pcount, poses, col, B);
-    }
-    if (nodes && !B.nodes.empty())
-        memcpy(nodes, B.nodes.data(), sizeof(BvhNode) * (size_t)std::min<int>(cap_nodes, (int)B.nodes.size()));
-    if (tri && !B.tri.empty()) memcpy(tri, B.tri.data(), 4 * (size_t)std::min<int>(cap_tri, (int)B.tri.size()));
-    if (out && !col.empty()) memcpy(out, col.data(), sizeof(srt_collider) * col.size());
-    if (bound) *bound = B.bound;
-    return (int)B.nodes.size();
+    const HcDeform h{first, count, n_verts, corner, recompute, center, P};
+    return refit_out(d, &h, n_ranges, pfirst, pcount, poses, nodes, cap_nodes, tri, cap_tri, out, bound);
 }
 
-// hc_pose_nearest for a deformed (and then posed) mesh: through the refitted BVH, or (hc_set_bvh(0)) the linear loop
+// hc_pose_nearest for a deformed (and then posed) mesh
 int hc_deform_nearest(const srt_scene_desc* d, int first, int count, int n_verts, const int32_t* corner,
                       const uint8_t* recompute, const double* center, const double* P, int n_ranges,
                       const int32_t* pfirst, const int32_t* pcount, const double* poses, const double* O,
                       const double* D, int64_t n, double* t, int32_t* id, double* orient) {
-    SceneView S = view_of(d);
-    std::vector<srt_collider> col(d->colliders, d->colliders + d->n_colliders);
-    if (!deform_and_refit(HcDeform{first, count, n_verts, corner, recompute, center, P}, col, g_bvh)) return -1;
-    if (n_ranges > 0) {
-        srt_scene_desc dd = *d;
-        const std::vector<srt_collider> rest = col;
-        dd.colliders = rest.data();
-        pose_and_refit(&dd, n_ranges, pfirst, pcount, poses, col, g_bvh);
-    }
-    S.col = col.data();
-    S.bvh_bound = g_bvh.bound;
-    for (int64_t i = 0; i < n; ++i) {
-        double tn, on;
-        bool ties;
-        int c = nearest_hit(S, d3{O[i], O[n + i], O[2 * n + i]}, d3{D[i], D[n + i], D[2 * n + i]}, tn, on, ties);
-        if (t) t[i] = tn;
-        if (id) id[i] = c;
-        if (orient) orient[i] = on;
-    }
-    return SRT_OK;
+    const HcDeform h{first, count, n_verts, corner, recompute, center, P};
+    return nearest_out(d, &h, n_ranges, pfirst, pcount, poses, O, D, n, t, id, orient);
 }
 
 }  // extern "C"

@@ -10,11 +10,11 @@
 //   (rt_pose.h, with the headers above: pose_triangle_record, k_pose_triangles, k_bvh_refit)
 //   (rt_deform.h, likewise: deform_triangle_record, k_deform_face_cross / _vertex_normals / _triangles)
 //   (this file)         the context and its frame slots, the MT host side, frame collection and gather,
-//                       srt_create and the options, scene upload, srt_pose_colliders,
-//                       srt_deform_topology and srt_deform_colliders
+//                       srt_create and the options, scene upload
 //   rt_render.h         render_impl, before srt_render and its siblings
 //   rt_api_trace.h      trace_impl, srt_trace and srt_shade*
 //   rt_api_entry.h      the single-kernel entry points, AOVs and denoise, device memory, srt_mt19937_uniforms
+//   rt_api_anim.h       srt_pose_colliders, srt_deform_topology, srt_deform_colliders over srt_ctx::mesh
 //   rt_api_group.h      communicators, srt_render_group*, allreduce, barrier
 //   rt_api_misc.h       host memory, the srt_debug_* hooks, srt_synchronize
 //
@@ -152,6 +152,73 @@ struct FrameSlot {
     FramePlan plan;
 };
 
+// Times of the N stages of an entry point's last call, between events on its stream (srt_debug_*_times), and how
+// many calls completed.  The events are made at their first mark and destroyed by ~srt_ctx.
+template <int N>
+struct StageTimer {
+    hipEvent_t ev[N + 1] = {};
+    double ms[N] = {};
+    int64_t calls = 0;
+    hipError_t mark(int k, hipStream_t st) {
+        if (!ev[k])
+            if (const hipError_t e = hipEventCreate(&ev[k])) return e;
+        return hipEventRecord(ev[k], st);
+    }
+    // after the stream is synchronised
+    hipError_t collect() {
+        for (int k = 0; k < N; ++k) {
+            float v = 0.0f;
+            if (const hipError_t e = hipEventElapsedTime(&v, ev[k], ev[k + 1])) return e;
+            ms[k] = v;
+        }
+        calls++;
+        return hipSuccess;
+    }
+};
+
+// A mesh registered by srt_deform_topology: `P` is DeformMesh::P for the copy in, `normals` whether any corner's
+// normal is recomputed
+struct DeformTopo {
+    DeformMesh m;
+    double* P = nullptr;
+    bool normals = false;
+};
+
+// The state of the animated triangle meshes (srt_pose_colliders, srt_deform_topology, srt_deform_colliders:
+// rt_api_anim.h, rt_pose.h, rt_deform.h).  Everything here belongs to the resident scene and starts afresh with an
+// upload (reset), except what reset() names.
+//   in scene_bufs (released with the scene): the collider table the kernels read (S.col) and its copy in the
+//     rest pose (as uploaded, or as last deformed), the BVH's nodes and leaf slots as plain pointers, the nodes
+//     grouped by height (rt_bvh.h BvhLevels), the registered meshes' tables and vertex arrays (allocated after
+//     every table of the upload)
+//   on the host: the rest table, the groups' offsets, the rest shape's bvh_bound, what the last pose call derived
+//     from its ranges alone, whether it left a range in another pose than the identity
+//   of the context: the pose call's range table and the two calls' stage timers
+struct MeshTables {
+    srt_collider* col_live = nullptr;
+    srt_collider* col_rest = nullptr;
+    BvhNode* bvh_dev = nullptr;
+    int32_t* bvh_tri_dev = nullptr;
+    int32_t* bvh_level_nodes = nullptr;
+    int bvh_ntri = 0;
+    std::vector<int32_t> bvh_level_offset;
+    std::vector<srt_collider> col_host;
+    float bvh_bound_rest = 0.0f;
+    PoseLayout pose_layout;
+    bool pose_active = false;
+    std::vector<DeformTopo> deform_meshes;
+    DevBuf<PoseRange> pose_ranges;
+    StageTimer<2> pose_timer;    // k_pose_triangles, the refit
+    StageTimer<3> deform_timer;  // the normals, the records, the refit
+    void reset() {
+        MeshTables fresh;
+        fresh.pose_ranges = std::move(pose_ranges);
+        fresh.pose_timer = pose_timer;
+        fresh.deform_timer = deform_timer;
+        *this = std::move(fresh);
+    }
+};
+
 struct srt_ctx {
     int device = 0;
     int max_blocks = 2048;
@@ -172,41 +239,7 @@ struct srt_ctx {
     int n_user_lights = 0;
     bool needs_inputs = false;
     DevList scene_bufs;
-    // posed triangle meshes (srt_pose_colliders, rt_pose.h).  In scene_bufs: the collider table the kernels
-    // read (S.col), its copy in the pose it was uploaded in, the BVH's nodes and leaf slots as plain pointers,
-    // the nodes grouped by height (rt_bvh.h BvhLevels).  On the host: the uploaded table, the groups' offsets,
-    // the built tree's bvh_bound, and what the last call derived from its ranges alone
-    srt_collider* col_live = nullptr;
-    srt_collider* col_rest = nullptr;
-    BvhNode* bvh_dev = nullptr;
-    int32_t* bvh_tri_dev = nullptr;
-    int32_t* bvh_level_nodes = nullptr;
-    int bvh_ntri = 0;
-    std::vector<int32_t> bvh_level_offset;
-    std::vector<srt_collider> col_host;
-    float bvh_bound_rest = 0.0f;
-    struct PoseLayout {
-        std::vector<int32_t> key;                   // first, count per range: valid for these
-        std::vector<std::array<double, 6>> box;     // rest vertex box per range
-        double static_reach = 0.0;                  // max |coordinate| of the triangles in no range
-    } pose_layout;
-    DevBuf<PoseRange> pose_ranges;
-    hipEvent_t pose_ev[3] = {nullptr, nullptr, nullptr};  // start, after k_pose_triangles, after the refit
-    double pose_ms[2] = {0.0, 0.0};                       // (srt_debug_pose_times) of the last call
-    int64_t pose_calls = 0;
-    bool pose_active = false;                             // the last call left a range in another pose than the identity
-    // deformed triangle meshes (srt_deform_topology / srt_deform_colliders, rt_deform.h): the registered meshes,
-    // whose tables and vertex arrays are in scene_bufs (allocated after every table of the upload, released with
-    // them); `P` is DeformMesh::P for the copy in, `normals` whether any corner's normal is recomputed
-    struct DeformTopo {
-        DeformMesh m;
-        double* P = nullptr;
-        bool normals = false;
-    };
-    std::vector<DeformTopo> deform_meshes;
-    hipEvent_t deform_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // start, after the normals, the records, the refit
-    double deform_ms[3] = {0.0, 0.0, 0.0};                           // (srt_debug_deform_times) of the last call
-    int64_t deform_calls = 0;
+    MeshTables mesh;  // what srt_pose_colliders / srt_deform_* rewrite of the scene (rt_api_anim.h)
     // texel pool (outside scene_bufs: survives re-uploads with the same texel_key)
     DevBuf<uint8_t> texels;
     uint64_t texel_key = 0;
@@ -1071,9 +1104,9 @@ srt_ctx::~srt_ctx() {
     scene_bufs.clear();
     if (comm) (void)ncclCommDestroy(comm);
     if (mt_done) (void)hipEventDestroy(mt_done);
-    for (hipEvent_t e : pose_ev)
+    for (hipEvent_t e : mesh.pose_timer.ev)
         if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : deform_ev)
+    for (hipEvent_t e : mesh.deform_timer.ev)
         if (e) (void)hipEventDestroy(e);
     if (mt_stream) (void)hipStreamDestroy(mt_stream);
 }
@@ -1369,8 +1402,8 @@ static int upload_tables(srt_ctx* c, const srt_scene_desc* d, SceneView& S, bool
     srt_light* lights;
     double *media, *f0, *ll, *imp;
     if ((rc = upload(c, d->colliders, d->n_colliders, &col))) return rc;
-    c->col_live = col;
-    c->col_host.assign(d->colliders, d->colliders + std::max(0, d->n_colliders));
+    c->mesh.col_live = col;
+    c->mesh.col_host.assign(d->colliders, d->colliders + std::max(0, d->n_colliders));
     if ((rc = upload(c, d->materials, d->n_materials, &mat))) return rc;
     const TexelPool tp = plan_texel_pool(d, d->texel_bytes > 0 && d->texels && !is_device_ptr(d->texels));
     if ((rc = upload(c, tp.tex.data(), d->n_textures, &tex))) return rc;
@@ -1404,17 +1437,17 @@ static int upload_tables(srt_ctx* c, const srt_scene_desc* d, SceneView& S, bool
     if ((rc = upload(c, B.lin.data(), (int64_t)B.lin.size(), &lin))) return rc;
     if ((rc = upload(c, B.tri.data(), (int64_t)B.tri.size(), &tri))) return rc;
     if ((rc = upload(c, B.nodes.data(), (int64_t)B.nodes.size(), &nodes))) return rc;
-    // what srt_pose_colliders needs, after every table the trace kernels read (whose allocations, and so
+    // what srt_pose_colliders (rt_api_anim.h) needs, after every table the trace kernels read (whose allocations, and so
     // addresses, stay what they were without it): the rest pose's copy of the collider table, the refit order
-    if ((rc = upload(c, d->colliders, d->n_colliders, &c->col_rest))) return rc;
+    if ((rc = upload(c, d->colliders, d->n_colliders, &c->mesh.col_rest))) return rc;
     BvhLevels lv;
     bvh_levels(B.nodes, lv);
-    if ((rc = upload(c, lv.nodes.data(), (int64_t)lv.nodes.size(), &c->bvh_level_nodes))) return rc;
-    c->bvh_level_offset = lv.offset;
-    c->bvh_dev = nodes;
-    c->bvh_tri_dev = tri;
-    c->bvh_ntri = (int)B.tri.size();
-    c->bvh_bound_rest = B.bound;
+    if ((rc = upload(c, lv.nodes.data(), (int64_t)lv.nodes.size(), &c->mesh.bvh_level_nodes))) return rc;
+    c->mesh.bvh_level_offset = lv.offset;
+    c->mesh.bvh_dev = nodes;
+    c->mesh.bvh_tri_dev = tri;
+    c->mesh.bvh_ntri = (int)B.tri.size();
+    c->mesh.bvh_bound_rest = B.bound;
     S.nlin = (int)B.lin.size();
     S.lin = (decltype(S.lin))lin;
     S.bvh_tri = (decltype(S.bvh_tri))tri;
@@ -1486,13 +1519,7 @@ int srt_upload_scene(srt_ctx* c, const srt_scene_desc* d) {
     HIP_TRY(hipStreamSynchronize(c->f->stream));
     c->scene_bufs.clear();
     c->has_scene = false;
-    c->col_live = c->col_rest = nullptr;
-    c->bvh_dev = nullptr;
-    c->bvh_tri_dev = c->bvh_level_nodes = nullptr;
-    c->bvh_level_offset.clear();
-    c->pose_layout = srt_ctx::PoseLayout{};
-    c->pose_active = false;
-    c->deform_meshes.clear();
+    c->mesh.reset();
     SceneView S{};
     bool lin_tri = false;
     if ((rc = upload_tables(c, d, S, lin_tri))) return rc;
@@ -1500,236 +1527,6 @@ int srt_upload_scene(srt_ctx* c, const srt_scene_desc* d) {
     c->has_scene = true;
     return SRT_OK;
 }
-
-// ---- srt_pose_colliders ----
-// what depends on the ranges alone, made once per set of ranges: their checks against the table (inside it,
-// triangles only, no overlap), each range's rest vertex box, the reach of the triangles in no range
-static int pose_layout_for(srt_ctx* c, int32_t n_ranges, const int32_t* first, const int32_t* count) {
-    std::vector<int32_t> key;
-    for (int r = 0; r < n_ranges; ++r) key.insert(key.end(), {first[r], count[r]});
-    srt_ctx::PoseLayout& PL = c->pose_layout;
-    if (!PL.key.empty() && PL.key == key) return SRT_OK;
-    PL = srt_ctx::PoseLayout{};
-    const int ncol = (int)c->col_host.size();
-    std::vector<uint8_t> posed((size_t)ncol, 0);
-    std::vector<std::array<double, 6>> box((size_t)n_ranges);
-    for (int r = 0; r < n_ranges; ++r) {
-        if (first[r] < 0 || count[r] < 1 || (int64_t)first[r] + count[r] > ncol)
-            return fail(SRT_ERR_ARG, "srt_pose_colliders: a range lies outside the collider table");
-        for (int i = first[r]; i < first[r] + count[r]; ++i) {
-            if (c->col_host[i].type != SRT_TRIANGLE)
-                return fail(SRT_ERR_ARG, "srt_pose_colliders: a range covers a collider that is no Triangle");
-            if (posed[i]) return fail(SRT_ERR_ARG, "srt_pose_colliders: the ranges overlap");
-            posed[i] = 1;
-        }
-        pose_range_box(c->col_host.data(), first[r], count[r], box[r].data());
-    }
-    PL.static_reach = pose_static_reach(c->col_host.data(), ncol, posed.data());
-    PL.key = std::move(key);
-    PL.box = std::move(box);
-    return SRT_OK;
-}
-
-int srt_pose_colliders(srt_ctx* c, int32_t n_ranges, const int32_t* first, const int32_t* count, const double* poses) {
-    if (!c) return fail(SRT_ERR_ARG, "srt_pose_colliders: null ctx");
-    if (!c->has_scene || !c->col_live || !c->col_rest) return fail(SRT_ERR_ARG, "srt_pose_colliders: no scene is resident");
-    if (n_ranges < 1 || !first || !count || !poses) return fail(SRT_ERR_ARG, "srt_pose_colliders: needs n_ranges >= 1 ranges and their poses");
-    for (int64_t k = 0; k < (int64_t)n_ranges * POSE_DOUBLES; ++k)
-        if (!std::isfinite(poses[k])) return fail(SRT_ERR_ARG, "srt_pose_colliders: a pose entry is not finite");
-    int rc;
-    if ((rc = pose_layout_for(c, n_ranges, first, count))) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    if ((rc = finish_async(c, nullptr))) return rc;  // frames in flight read the tables rewritten below
-    const hipStream_t st = c->f->stream;
-    HIP_TRY(hipStreamSynchronize(st));
-    for (hipEvent_t& e : c->pose_ev)
-        if (!e) HIP_TRY(hipEventCreate(&e));
-    std::vector<PoseRange> R((size_t)n_ranges);
-    int64_t total = 0;
-    bool all_identity = true;
-    double reach = c->pose_layout.static_reach;
-    for (int r = 0; r < n_ranges; ++r) {
-        R[r].first = first[r];
-        R[r].count = count[r];
-        R[r].start = total;
-        total += count[r];
-        memcpy(R[r].pose, poses + (size_t)r * POSE_DOUBLES, sizeof R[r].pose);
-        all_identity = all_identity && pose_is_identity(R[r].pose);
-        const std::array<double, 6>& b = c->pose_layout.box[r];
-        reach = std::max(reach, pose_box_reach(b.data(), b.data() + 3, R[r].pose));
-    }
-    if ((rc = c->pose_ranges.ensure(n_ranges))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->pose_ranges, R.data(), R.size() * sizeof(PoseRange), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(c->pose_ev[0], st));
-    hipLaunchKernelGGL(k_pose_triangles, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, c->col_rest,
-                       c->col_live, c->pose_ranges.p, n_ranges, total, (int)c->col_host.size());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->pose_ev[1], st));
-    if (c->S.bvh_nodes > 0) {
-        // height by height, leaves' parents first: a group reads the boxes the groups before it wrote
-        for (size_t h = 0; h + 1 < c->bvh_level_offset.size(); ++h) {
-            const int off = c->bvh_level_offset[h], n = c->bvh_level_offset[h + 1] - off;
-            if (n <= 0) continue;
-            hipLaunchKernelGGL(k_bvh_refit, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, st, c->bvh_dev,
-                               c->S.bvh_nodes, c->bvh_tri_dev, c->bvh_ntri, c->col_live, (int)c->col_host.size(),
-                               c->bvh_level_nodes + off, n);
-            HIP_TRY(hipGetLastError());
-        }
-        c->S.bvh_bound = all_identity ? c->bvh_bound_rest : pose_bound(reach);
-    }
-    c->pose_active = !all_identity;
-    HIP_TRY(hipEventRecord(c->pose_ev[2], st));
-    HIP_TRY(hipStreamSynchronize(st));  // the next frame may run on another slot's stream
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->pose_ev[0], c->pose_ev[1]));
-    c->pose_ms[0] = ms;
-    HIP_TRY(hipEventElapsedTime(&ms, c->pose_ev[1], c->pose_ev[2]));
-    c->pose_ms[1] = ms;
-    c->pose_calls++;
-    return SRT_OK;
-}
-
-int srt_debug_pose_times(srt_ctx* c, double* ms_pose, double* ms_refit, int64_t* calls) {
-    if (!c) return fail(SRT_ERR_ARG, "null ctx");
-    if (ms_pose) *ms_pose = c->pose_ms[0];
-    if (ms_refit) *ms_refit = c->pose_ms[1];
-    if (calls) *calls = c->pose_calls;
-    return SRT_OK;
-}
-
-// ---- srt_deform_topology, srt_deform_colliders ----
-int srt_deform_topology(srt_ctx* c, int32_t first, int32_t count, int32_t n_verts, const int32_t* corners,
-                        const double* center, const uint8_t* recompute) {
-    if (!c) return fail(SRT_ERR_ARG, "srt_deform_topology: null ctx");
-    if (!c->has_scene || !c->col_live || !c->col_rest) return fail(SRT_ERR_ARG, "srt_deform_topology: no scene is resident");
-    if (!corners || !center || !recompute) return fail(SRT_ERR_ARG, "srt_deform_topology: needs corners, center and the corner flags");
-    const int ncol = (int)c->col_host.size();
-    if (first < 0 || count < 1 || (int64_t)first + count > ncol)
-        return fail(SRT_ERR_ARG, "srt_deform_topology: the range lies outside the collider table");
-    for (int i = first; i < first + count; ++i)
-        if (c->col_host[i].type != SRT_TRIANGLE)
-            return fail(SRT_ERR_ARG, "srt_deform_topology: the range covers a collider that is no Triangle");
-    for (const srt_ctx::DeformTopo& t : c->deform_meshes)
-        if (first < t.m.first + t.m.count && t.m.first < first + count)
-            return fail(SRT_ERR_ARG, "srt_deform_topology: the range overlaps a registered one");
-    if (n_verts < 1) return fail(SRT_ERR_ARG, "srt_deform_topology: needs n_verts >= 1");
-    bool normals = false;
-    for (int64_t j = 0; j < 3 * (int64_t)count; ++j) {
-        if (corners[j] < 0 || corners[j] >= n_verts)
-            return fail(SRT_ERR_ARG, "srt_deform_topology: a corner index lies outside [0, n_verts)");
-        normals = normals || recompute[j];
-    }
-    for (int k = 0; k < 3; ++k)
-        if (!std::isfinite(center[k])) return fail(SRT_ERR_ARG, "srt_deform_topology: center is not finite");
-    HIP_TRY(hipSetDevice(c->device));
-    std::vector<int32_t> offset, list;
-    deform_csr(corners, count, n_verts, offset, list);
-    srt_ctx::DeformTopo t;
-    int32_t *d_corner, *d_offset, *d_list;
-    uint8_t* d_flag;
-    HIP_TRY(c->scene_bufs.in(&d_corner, corners, 3 * (int64_t)count));
-    HIP_TRY(c->scene_bufs.in(&d_flag, recompute, 3 * (int64_t)count));
-    HIP_TRY(c->scene_bufs.in(&d_offset, (const int32_t*)offset.data(), (int64_t)offset.size()));
-    HIP_TRY(c->scene_bufs.in(&d_list, (const int32_t*)list.data(), (int64_t)list.size()));
-    HIP_TRY(c->scene_bufs.alloc(&t.P, 3 * (int64_t)n_verts));
-    HIP_TRY(c->scene_bufs.alloc(&t.m.face_cross, 3 * (int64_t)count));
-    HIP_TRY(c->scene_bufs.alloc(&t.m.vertex_sum, 3 * (int64_t)n_verts));
-    t.m.first = first, t.m.count = count, t.m.n_verts = n_verts;
-    t.m.corner = d_corner, t.m.recompute = d_flag, t.m.csr_offset = d_offset, t.m.csr_corner = d_list;
-    t.m.P = t.P;
-    for (int k = 0; k < 3; ++k) t.m.center[k] = center[k];
-    t.normals = normals;
-    c->deform_meshes.push_back(t);
-    return SRT_OK;
-}
-
-int srt_deform_colliders(srt_ctx* c, int32_t n_meshes, const int32_t* first, const int32_t* count,
-                         const double* const* verts) {
-    if (!c) return fail(SRT_ERR_ARG, "srt_deform_colliders: null ctx");
-    if (!c->has_scene || !c->col_live || !c->col_rest) return fail(SRT_ERR_ARG, "srt_deform_colliders: no scene is resident");
-    if (n_meshes < 1 || !first || !count || !verts) return fail(SRT_ERR_ARG, "srt_deform_colliders: needs n_meshes >= 1 ranges and their vertex arrays");
-    std::vector<int> which((size_t)n_meshes, -1);
-    for (int r = 0; r < n_meshes; ++r) {
-        for (size_t k = 0; k < c->deform_meshes.size(); ++k)
-            if (c->deform_meshes[k].m.first == first[r] && c->deform_meshes[k].m.count == count[r]) which[r] = (int)k;
-        if (which[r] < 0) return fail(SRT_ERR_ARG, "srt_deform_colliders: a range is not registered (srt_deform_topology)");
-        for (int q = 0; q < r; ++q)
-            if (which[q] == which[r]) return fail(SRT_ERR_ARG, "srt_deform_colliders: a range is named twice");
-        if (!verts[r]) return fail(SRT_ERR_ARG, "srt_deform_colliders: a vertex array is null");
-        const int64_t n = 3 * (int64_t)c->deform_meshes[which[r]].m.n_verts;
-        for (int64_t j = 0; j < n; ++j)
-            if (!std::isfinite(verts[r][j])) return fail(SRT_ERR_ARG, "srt_deform_colliders: a coordinate is not finite");
-    }
-    int rc;
-    HIP_TRY(hipSetDevice(c->device));
-    if ((rc = finish_async(c, nullptr))) return rc;  // frames in flight read the tables rewritten below
-    const hipStream_t st = c->f->stream;
-    HIP_TRY(hipStreamSynchronize(st));
-    for (hipEvent_t& e : c->deform_ev)
-        if (!e) HIP_TRY(hipEventCreate(&e));
-    const int ncol = (int)c->col_host.size();
-    for (int r = 0; r < n_meshes; ++r) {
-        const srt_ctx::DeformTopo& t = c->deform_meshes[which[r]];
-        HIP_TRY(hipMemcpyAsync(t.P, verts[r], sizeof(double) * 3 * (size_t)t.m.n_verts, hipMemcpyHostToDevice, st));
-    }
-    HIP_TRY(hipEventRecord(c->deform_ev[0], st));
-    for (int r = 0; r < n_meshes; ++r) {
-        const srt_ctx::DeformTopo& t = c->deform_meshes[which[r]];
-        if (!t.normals) continue;
-        hipLaunchKernelGGL(k_deform_face_cross, dim3((unsigned)((t.m.count + 255) / 256)), dim3(256), 0, st, t.m);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_deform_vertex_normals, dim3((unsigned)((t.m.n_verts + 255) / 256)), dim3(256), 0, st, t.m);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(c->deform_ev[1], st));
-    for (int r = 0; r < n_meshes; ++r) {
-        const srt_ctx::DeformTopo& t = c->deform_meshes[which[r]];
-        hipLaunchKernelGGL(k_deform_triangles, dim3((unsigned)((t.m.count + 255) / 256)), dim3(256), 0, st, t.m,
-                           c->col_rest, c->col_live, ncol);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(c->deform_ev[2], st));
-    if (c->S.bvh_nodes > 0)
-        for (size_t h = 0; h + 1 < c->bvh_level_offset.size(); ++h) {
-            const int off = c->bvh_level_offset[h], n = c->bvh_level_offset[h + 1] - off;
-            if (n <= 0) continue;
-            hipLaunchKernelGGL(k_bvh_refit, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, st, c->bvh_dev,
-                               c->S.bvh_nodes, c->bvh_tri_dev, c->bvh_ntri, c->col_live, ncol, c->bvh_level_nodes + off, n);
-            HIP_TRY(hipGetLastError());
-        }
-    HIP_TRY(hipEventRecord(c->deform_ev[3], st));
-    // the host's copy of the rest table follows (a later pose call takes its boxes and reach from it)
-    for (int r = 0; r < n_meshes; ++r) {
-        const DeformMesh& m = c->deform_meshes[which[r]].m;
-        HIP_TRY(hipMemcpyAsync(c->col_host.data() + m.first, c->col_rest + m.first, sizeof(srt_collider) * (size_t)m.count,
-                               hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));  // the next frame may run on another slot's stream
-    c->pose_layout = srt_ctx::PoseLayout{};
-    if (c->S.bvh_nodes > 0) {
-        const float bound = pose_bound(pose_static_reach(c->col_host.data(), ncol, std::vector<uint8_t>((size_t)ncol, 0).data()));
-        // (ranges outside this call may still be posed: the bound that held for their boxes goes on holding)
-        c->S.bvh_bound = c->pose_active ? std::max(c->S.bvh_bound, bound) : bound;
-        c->bvh_bound_rest = bound;
-    }
-    float ms = 0.0f;
-    for (int k = 0; k < 3; ++k) {
-        HIP_TRY(hipEventElapsedTime(&ms, c->deform_ev[k], c->deform_ev[k + 1]));
-        c->deform_ms[k] = ms;
-    }
-    c->deform_calls++;
-    return SRT_OK;
-}
-
-int srt_debug_deform_times(srt_ctx* c, double* ms_normals, double* ms_records, double* ms_refit, int64_t* calls) {
-    if (!c) return fail(SRT_ERR_ARG, "null ctx");
-    if (ms_normals) *ms_normals = c->deform_ms[0];
-    if (ms_records) *ms_records = c->deform_ms[1];
-    if (ms_refit) *ms_refit = c->deform_ms[2];
-    if (calls) *calls = c->deform_calls;
-    return SRT_OK;
-}
-
 
 }  // extern "C"
 #include "rt_render.h"  // render_impl: srt_render and srt_render_prefetch
@@ -1759,5 +1556,6 @@ int srt_stream(srt_ctx* c, void** stream) {
 
 #include "rt_api_trace.h"
 #include "rt_api_entry.h"
+#include "rt_api_anim.h"
 #include "rt_api_group.h"
 #include "rt_api_misc.h"

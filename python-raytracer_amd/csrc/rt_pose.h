@@ -1,6 +1,6 @@
 // rt_pose.h -- rigidly posed triangle meshes: the collider records of a mesh recomputed on the device
 // from a resident copy in the pose the scene was uploaded in (the rest pose), and the BVH's boxes refitted
-// over the posed vertices (srt_pose_colliders in rt_kernels.hip; the CPU check harness rt_hostcheck.cpp
+// over the posed vertices (srt_pose_colliders in rt_api_anim.h; the CPU check harness rt_hostcheck.cpp
 // runs the same functions).  The trace kernels read the rewritten tables as they read uploaded ones.
 //
 // A pose is 12 doubles, R row-major then T (the layout of srt_temporal_accumulate's motion rows).  A vertex
@@ -9,6 +9,10 @@
 // sightpy's Triangle_Collider computes it (geometry/triangle.py, _lower.collider_record), in its
 // operation order, contraction off.  The identity pose (R = I and T = 0 exactly) copies the rest record.
 #pragma once
+
+#include <array>
+#include <string>
+#include <vector>
 
 #include "rt_bvh.h"
 #include "rt_device.h"
@@ -155,17 +159,69 @@ inline void pose_range_box(const srt_collider* col, int first, int count, double
             box[3 + v % 3] = std::max(box[3 + v % 3], col[i].p[v]);
         }
 }
-// max |vertex coordinate| of the triangles among col[0, ncol) that `posed` does not mark
+// max |vertex coordinate| of the triangles among col[0, ncol) that `posed` does not mark (null: marks none)
 inline double pose_static_reach(const srt_collider* col, int ncol, const uint8_t* posed) {
     double reach = 0.0;
     for (int i = 0; i < ncol; ++i)
-        if (!posed[i] && col[i].type == SRT_TRIANGLE)
+        if (!(posed && posed[i]) && col[i].type == SRT_TRIANGLE)
             for (int v = 6; v < 15; ++v) reach = std::max(reach, std::fabs(col[i].p[v]));
     return reach;
 }
 // SceneView::bvh_bound for a tree refitted over vertices within `reach` of the origin: the build's inflation
 // twice over (the refit inflates by its own, rounded vertices' reach), rounded up
 inline float pose_bound(double reach) { return bvh_round_up(reach * (1.0 + 1e-12) + 2e-9 * (1.0 + reach)); }
+
+// ---- SceneView::bvh_bound after a pose or a deformation: the host-side rule, which srt_pose_colliders and
+// srt_deform_colliders (rt_api_anim.h) and the CPU check harness (rt_hostcheck.cpp) both run ----
+// Why col[first, first + count) is no range of Triangle colliders of the table col[0, ncol), as the words that
+// follow the refusal's subject ("a range", "the range"); null when it is one.
+inline const char* triangle_range_fault(const srt_collider* col, int ncol, int first, int count) {
+    if (first < 0 || count < 1 || (int64_t)first + count > ncol) return " lies outside the collider table";
+    for (int i = first; i < first + count; ++i)
+        if (col[i].type != SRT_TRIANGLE) return " covers a collider that is no Triangle";
+    return nullptr;
+}
+
+// What a set of posed ranges fixes whatever their poses are (so it is kept while the ranges stay the same: `key`).
+struct PoseLayout {
+    std::vector<int32_t> key;                // first, count per range: valid for these, over an unchanged rest table
+    std::vector<std::array<double, 6>> box;  // rest vertex box per range
+    double static_reach = 0.0;               // max |coordinate| of the triangles in no range
+};
+// The layout of `n_ranges` ranges over the rest table col[0, ncol), each range checked in turn (inside the table,
+// triangles only, no overlap with an earlier one).  Returns the refusal, or an empty string with `PL` filled.
+inline std::string pose_layout_build(const srt_collider* col, int ncol, int n_ranges, const int32_t* first,
+                                     const int32_t* count, PoseLayout& PL) {
+    PL = PoseLayout{};
+    std::vector<uint8_t> posed((size_t)ncol, 0);
+    std::vector<std::array<double, 6>> box((size_t)n_ranges);
+    for (int r = 0; r < n_ranges; ++r) {
+        if (const char* fault = triangle_range_fault(col, ncol, first[r], count[r])) return std::string("a range") + fault;
+        for (int i = first[r]; i < first[r] + count[r]; ++i) {
+            if (posed[i]) return "the ranges overlap";
+            posed[i] = 1;
+        }
+        pose_range_box(col, first[r], count[r], box[r].data());
+    }
+    for (int r = 0; r < n_ranges; ++r) PL.key.insert(PL.key.end(), {first[r], count[r]});
+    PL.static_reach = pose_static_reach(col, ncol, posed.data());
+    PL.box = std::move(box);
+    return std::string();
+}
+// The bound of the tree refitted with the layout's ranges under `poses` (POSE_DOUBLES each); `rest_bound` is the
+// bound of the rest shape's tree, which holds again when every pose is the identity (`all_identity`).
+inline float pose_layout_bound(const PoseLayout& PL, const double* poses, float rest_bound, bool& all_identity) {
+    double reach = PL.static_reach;
+    all_identity = true;
+    for (size_t r = 0; r < PL.box.size(); ++r) {
+        const double* pose = poses + r * POSE_DOUBLES;
+        all_identity = all_identity && pose_is_identity(pose);
+        reach = std::max(reach, pose_box_reach(PL.box[r].data(), PL.box[r].data() + 3, pose));
+    }
+    return all_identity ? rest_bound : pose_bound(reach);
+}
+// The bound of the tree refitted over the table col[0, ncol) as it stands (a deformation's new rest shape).
+inline float rest_table_bound(const srt_collider* col, int ncol) { return pose_bound(pose_static_reach(col, ncol, nullptr)); }
 
 #if defined(__HIPCC__)
 // One thread per triangle of the posed ranges (`total` in all): the live record from the rest record.

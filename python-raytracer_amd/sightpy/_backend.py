@@ -14,14 +14,35 @@ from ._lower import lower_scene, camera_desc, collider_record, POSE_IDENTITY
 from ._motion import collider_motion, count_rows, pose_motion
 from .utils.vector3 import vec3
 
-_STATE = {"lib": None, "ctx": None, "device": None, "scene_sig": {}, "scene_inputs": {}, "buffers": {}, "pinned": {}, "group": None}
-# device-posed meshes (TriangleMesh.set_pose): the poses resident per context, and how often upload() called
-# srt_upload_scene and srt_pose_colliders
-_STATE.update({"pose_sig": {}, "uploads": 0, "pose_calls": 0})
-# device-deformed meshes (TriangleMesh.set_vertices): per context, the vertex version resident for each mesh range
-# that is not in its loaded shape ({(first, count): (mesh key, version)}) and the ranges whose topology is
-# registered since the last upload; how often upload() called srt_deform_colliders
-_STATE.update({"vert_sig": {}, "deform_topology": {}, "deform_calls": 0})
+_STATE = {"lib": None, "ctx": None, "device": None, "resident": {}, "buffers": {}, "pinned": {}, "group": None}
+# how often upload() called srt_upload_scene, srt_pose_colliders and srt_deform_colliders
+_STATE.update({"uploads": 0, "pose_calls": 0, "deform_calls": 0})
+
+
+class Resident:
+    """What upload() knows to be resident in one context (_STATE["resident"], by the context's address)."""
+
+    def __init__(self):
+        self.forget()
+        self.per_hit_inputs = False  # the scene is shaded with per-hit inputs (a user texture / Light, _hybrid.py)
+
+    def forget(self):
+        """Nothing is known to be resident (per_hit_inputs stays until an upload sets it)."""
+        self.scene = None      # Lowered.signature() of the uploaded tables
+        self.poses = ()        # _pose_sig() of the poses of the device-posed meshes (TriangleMesh.set_pose)
+        self.verts = {}        # {(first, count): (mesh key, version)} of the ranges not in their loaded shape
+        self.topology = set()  # the ranges registered with srt_deform_topology since the upload
+
+
+def resident(ctx):
+    """The residency record of `ctx`."""
+    return _STATE["resident"].setdefault(_addr(ctx), Resident())
+
+
+def forget_resident(ctx=None):
+    """Forget what is resident in `ctx` (default: in every context): the next upload() there uploads."""
+    for res in _STATE["resident"].values() if ctx is None else [resident(ctx)]:
+        res.forget()
 
 
 class RenderResult:
@@ -130,83 +151,91 @@ def _vert_version(p):
     return None if p.get("deform") is None else (p["key"], p["vver"])
 
 
+def plan_upload(res, L, force=False):
+    """The library calls that make the Lowered `L` resident where the record `res` (a Resident) is, in order:
+    ("upload", signature), ("topology", range) per range, ("deform", [range, ...]), ("pose",).  Reads `res`,
+    changes nothing and calls nothing.  The poses of device-posed meshes are no part of the tables and are compared on their own:
+    when only they changed, the plan is one pose call.  Neither are the vertex arrays of deformed meshes
+    (TriangleMesh.set_vertices): when the version resident for a mesh is not the one wanted, a deform call for
+    those meshes (their topology registered first, once per upload), which leaves them in the identity pose, so a
+    pose call follows if any pose is another."""
+    want, identity = _pose_sig(L.posed), _pose_sig(L.posed, identity=True)
+    wanted = {(p["first"], p["count"]): _vert_version(p) for p in L.posed if p.get("deform") is not None}
+    verts, topology, poses = res.verts, res.topology, res.poses
+    steps = []
+    # a deformed range resident that no deformed mesh of this scene claims: the tables are another shape's than the
+    # signature says (the mesh went back to its loaded shape without an array to restore it from -- invalidate() --
+    # or this is another scene with the same tables, a fresh Scene of the same OBJ for one): only an upload restores it
+    sig = L.signature()
+    if force or set(verts) - set(wanted) or sig != res.scene:
+        steps.append(("upload", sig))
+        verts, topology, poses = {}, set(), identity  # (every mesh in its rest pose, at its loaded vertices)
+    changed = [rng for rng, version in wanted.items() if verts.get(rng) != version]
+    if changed:
+        steps += [("topology", rng) for rng in changed if rng not in topology]
+        steps.append(("deform", changed))
+        if want != identity:
+            poses = ()  # (the deformed ranges are back in the identity pose)
+    if want != poses:
+        steps.append(("pose",))
+    return steps
+
+
 def upload(scene, extra_media=(), force=False, ctx=None):
-    """Lower and upload `scene` to `ctx` (default: the process context) unless the identical tables
-    are already resident there.  The poses of device-posed meshes (TriangleMesh.set_pose) are no part of the
-    tables and are compared on their own: when only they changed, srt_pose_colliders alone is called
-    (_STATE["uploads"] and _STATE["pose_calls"] count the two kinds of call).  Neither are the vertex arrays of
-    deformed meshes (TriangleMesh.set_vertices): when the version resident for a mesh is not the one wanted,
-    srt_deform_colliders is called for those meshes (their topology registered first, once per upload), which
-    leaves them in the identity pose, so srt_pose_colliders follows if any pose is another
-    (_STATE["deform_calls"]).  Whenever a deformed range is resident that no deformed mesh of `scene` claims -- the
-    mesh went back to its loaded shape by invalidate(), or `scene` is another scene with the same tables -- the
-    scene is uploaded, although its signature is the resident one."""
+    """Lower `scene` and make it resident in `ctx` (default: the process context) by the calls of plan_upload():
+    none when the identical tables, poses and vertices are already there (_STATE["uploads"], ["pose_calls"] and
+    ["deform_calls"] count the calls of each kind).  What a call is about to rewrite is forgotten before it and
+    recorded after it returned success, so after a call that raised the next upload() makes it again."""
     lib = library()
     if ctx is None:
         ctx = context()[1]
     L = lower_scene(scene, extra_media)
-    sig = L.signature()
-    key = ctx.value if isinstance(ctx, ctypes.c_void_p) else int(ctx)
-    want = _pose_sig(L.posed)
-    if want != _pose_sig(L.posed, identity=True) and len(devices()) > 1:
+    want, identity = _pose_sig(L.posed), _pose_sig(L.posed, identity=True)
+    if want != identity and len(devices()) > 1:
         raise NotImplementedError("a posed TriangleMesh (set_pose) renders on one GPU; %d are selected "
                                   "($SIGHTPY_DEVICES)" % len(devices()))
     if any(p.get("deform") is not None for p in L.posed) and len(devices()) > 1:
         raise NotImplementedError("a deformed TriangleMesh (set_vertices) renders on one GPU; %d are selected "
                                   "($SIGHTPY_DEVICES)" % len(devices()))
-    # a deformed range resident that no deformed mesh of this scene claims: the tables are another shape's than the
-    # signature says (the mesh went back to its loaded shape without an array to restore it from -- invalidate() --
-    # or this is another scene with the same tables, a fresh Scene of the same OBJ for one): only an upload restores it
-    resident = _STATE["vert_sig"].get(key, {})
-    if set(resident) - {(p["first"], p["count"]) for p in L.posed if p.get("deform") is not None}:
-        force = True
-    if force or sig != _STATE["scene_sig"].get(key):
-        _STATE["scene_sig"].pop(key, None)
-        _STATE["pose_sig"].pop(key, None)
-        _STATE["vert_sig"].pop(key, None)
-        _STATE["deform_topology"].pop(key, None)
-        N.check(lib, lib.srt_upload_scene(ctx, ctypes.byref(L.desc())))
-        _STATE["uploads"] += 1
-        _STATE["scene_sig"][key] = sig
-        _STATE["pose_sig"][key] = _pose_sig(L.posed, identity=True)  # (an upload leaves every mesh in its rest pose)
-        _STATE["vert_sig"][key] = {}                                 # (... and at its loaded vertices)
-        _STATE["deform_topology"][key] = set()
-        # a scene shaded with per-hit inputs (a user texture / Light, _hybrid.py): the library refuses
-        # every whole-frame entry point on it, srt_render_prefetch included
-        _STATE["scene_inputs"][key] = bool((L.materials["flags"] & N.MF_HIT_ALBEDO).any()
-                                           or (L.lights["type"] == N.LIGHT_USER).any())
-    resident = _STATE["vert_sig"].setdefault(key, {})
-    changed = [p for p in L.posed if p.get("deform") is not None and resident.get((p["first"], p["count"])) != _vert_version(p)]
-    if changed:
-        registered = _STATE["deform_topology"].setdefault(key, set())
-        for p in changed:
-            rng, d = (p["first"], p["count"]), p["deform"]
-            resident.pop(rng, None)
-            if rng not in registered:
-                corners = np.ascontiguousarray(d["corners"], dtype=np.int32)
-                flags = np.ascontiguousarray(d["recompute"], dtype=np.uint8)
-                center = np.ascontiguousarray(d["center"], dtype=np.float64)
-                N.check(lib, lib.srt_deform_topology(ctx, rng[0], rng[1], len(d["verts"]), N.ptr(corners), N.ptr(center),
-                                                     N.ptr(flags)))
-                registered.add(rng)
-        first = np.array([p["first"] for p in changed], dtype=np.int32)
-        count = np.array([p["count"] for p in changed], dtype=np.int32)
-        verts = [np.ascontiguousarray(p["deform"]["verts"], dtype=np.float64) for p in changed]
-        ptrs = (ctypes.c_void_p * len(verts))(*[N.ptr(v) for v in verts])
-        N.check(lib, lib.srt_deform_colliders(ctx, len(first), N.ptr(first), N.ptr(count), ptrs))
-        _STATE["deform_calls"] += 1
-        for p in changed:
-            resident[(p["first"], p["count"])] = _vert_version(p)
-        if want != _pose_sig(L.posed, identity=True):
-            _STATE["pose_sig"].pop(key, None)  # (the deformed ranges are back in the identity pose)
-    if want != _STATE["pose_sig"].get(key, ()):
-        _STATE["pose_sig"].pop(key, None)
-        first = np.array([p["first"] for p in L.posed], dtype=np.int32)
-        count = np.array([p["count"] for p in L.posed], dtype=np.int32)
-        poses = np.ascontiguousarray([p["pose"] for p in L.posed], dtype=np.float64)
-        N.check(lib, lib.srt_pose_colliders(ctx, len(first), N.ptr(first), N.ptr(count), N.ptr(poses)))
-        _STATE["pose_calls"] += 1
-        _STATE["pose_sig"][key] = want
+    res = resident(ctx)
+    by_range = {(p["first"], p["count"]): p for p in L.posed}
+    for step in plan_upload(res, L, force):
+        if step[0] == "upload":
+            res.forget()
+            N.check(lib, lib.srt_upload_scene(ctx, ctypes.byref(L.desc())))
+            _STATE["uploads"] += 1
+            res.scene, res.poses = step[1], identity
+            # the library refuses every whole-frame entry point on such a scene, srt_render_prefetch included
+            res.per_hit_inputs = bool((L.materials["flags"] & N.MF_HIT_ALBEDO).any()
+                                      or (L.lights["type"] == N.LIGHT_USER).any())
+        elif step[0] == "topology":
+            rng, d = step[1], by_range[step[1]]["deform"]
+            corners = np.ascontiguousarray(d["corners"], dtype=np.int32)
+            flags = np.ascontiguousarray(d["recompute"], dtype=np.uint8)
+            center = np.ascontiguousarray(d["center"], dtype=np.float64)
+            N.check(lib, lib.srt_deform_topology(ctx, rng[0], rng[1], len(d["verts"]), N.ptr(corners), N.ptr(center),
+                                                 N.ptr(flags)))
+            res.topology.add(rng)
+        elif step[0] == "deform":
+            for rng in step[1]:
+                res.verts.pop(rng, None)
+            first, count = (np.array(v, dtype=np.int32) for v in zip(*step[1]))
+            verts = [np.ascontiguousarray(by_range[rng]["deform"]["verts"], dtype=np.float64) for rng in step[1]]
+            ptrs = (ctypes.c_void_p * len(verts))(*[N.ptr(v) for v in verts])
+            N.check(lib, lib.srt_deform_colliders(ctx, len(first), N.ptr(first), N.ptr(count), ptrs))
+            _STATE["deform_calls"] += 1
+            for rng in step[1]:
+                res.verts[rng] = _vert_version(by_range[rng])
+            if want != identity:
+                res.poses = ()  # (the deformed ranges are back in the identity pose)
+        else:
+            res.poses = ()
+            first = np.array([p["first"] for p in L.posed], dtype=np.int32)
+            count = np.array([p["count"] for p in L.posed], dtype=np.int32)
+            poses = np.ascontiguousarray([p["pose"] for p in L.posed], dtype=np.float64)
+            N.check(lib, lib.srt_pose_colliders(ctx, len(first), N.ptr(first), N.ptr(count), N.ptr(poses)))
+            _STATE["pose_calls"] += 1
+            res.poses = want
     return L
 
 
@@ -453,7 +482,7 @@ def render_scene(scene, spp, jitter=None, seed=None, batch_size=None, rows=None,
     a.flags = (0 if want_rgb else N.RENDER_RGB_LOCAL) | (N.RENDER_RGBX if rgbx else 0)
     # (the prefetch runs before this frame's scene replaces the resident one: not while that one is a
     # per-hit-inputs scene, on which the library refuses it)
-    if mt and prefetch and rows_arr is None and nrows == H and not _STATE["scene_inputs"].get(ctx.value):
+    if mt and prefetch and rows_arr is None and nrows == H and not resident(ctx).per_hit_inputs:
         N.check(lib, lib.srt_render_prefetch(ctx, ctypes.byref(cd), ctypes.byref(a)))
     upload(scene)
     rgb = np.empty((3, npix)) if want_rgb and rgb_device is None else None

@@ -221,6 +221,22 @@ def mesh_scene(obj_path, width=64, height=48, depth=3, center=(0.35, 0.05, -1.0)
     return sc
 
 
+def plain_mesh_scene(obj_path):
+    """mesh_scene's mesh over a floor without an image anywhere (no texel pool, whose key names image
+    objects): two scenes built by this function have equal signatures."""
+    red = Glossy(diff_color=rgb(0.6, 0.1, 0.1), n=vec3(1.5 + 0.2j, 1.5 + 0.2j, 1.5 + 0.2j), roughness=0.2,
+                 spec_coeff=0.4, diff_coeff=0.8)
+    grey = Glossy(diff_color=rgb(0.5, 0.5, 0.5), n=vec3(1.2 + 0.3j, 1.2 + 0.3j, 1.1 + 0.3j), roughness=0.2,
+                  spec_coeff=0.3, diff_coeff=0.9)
+    sc = Scene(ambient_color=rgb(0.05, 0.05, 0.05))
+    sc.add_Camera(look_from=vec3(0.3, 0.6, 1.8), look_at=vec3(0.0, 0.0, -1.0), screen_width=64, screen_height=48)
+    sc.add_DirectionalLight(Ldir=vec3(0.52, 0.45, -0.5), color=rgb(0.5, 0.5, 0.5))
+    sc.add(TriangleMesh(obj_path, center=vec3(0.35, 0.05, -1.0), material=red, max_ray_depth=3))
+    sc.add(Plane(material=grey, center=vec3(0, -0.5, -2.0), width=40.0, height=40.0, u_axis=vec3(1.0, 0, 0),
+                 v_axis=vec3(0, 0, -1.0), max_ray_depth=3))
+    return sc
+
+
 def mesh_bench(width=1920, height=1080, depth=3, subdiv=5):
     """Bench workload for the BVH: mesh_scene with an icosphere of 20 * 4**subdiv triangles."""
     import os

@@ -162,7 +162,7 @@ def test_gpu_linear_loop_against_the_refitted_bvh(objs):
         off = _render(sc, jit)
     finally:
         _set_option("bvh", 1)
-        B._STATE["scene_sig"].clear()
+        B.forget_resident()
     assert np.array_equal(on.hit_ids, off.hit_ids)
     assert np.array_equal(on.rgb, off.rgb) and np.array_equal(on.srgb8, off.srgb8)
     assert np.isin(on.hit_ids, _mesh_ids(sc)).mean() > 0.02
@@ -176,7 +176,7 @@ def test_gpu_no_drift_over_a_deformation_sequence(objs):
     mesh = MD.mesh_of(sc)
     V = mesh.file_vertices
     jit = _jitter(sc)
-    B._STATE["scene_sig"].clear()
+    B.forget_resident()
     frames, cost = [], []
     for P in (None, MD.twist(V), MD.bulge(V), V):
         if P is not None:
@@ -204,24 +204,6 @@ def test_gpu_no_drift_over_a_deformation_sequence(objs):
     assert calls.value >= 5 and all(m.value >= 0.0 for m in ms) and ms[1].value > 0.0 and ms[2].value > 0.0
 
 
-def _plain_scene(path):
-    """scenes.mesh_scene's mesh over a floor without an image anywhere (no texel pool, whose key names image
-    objects): two scenes built by this function have equal signatures."""
-    from sightpy import Glossy, Plane, Scene, rgb
-
-    red = Glossy(diff_color=rgb(0.6, 0.1, 0.1), n=vec3(1.5 + 0.2j, 1.5 + 0.2j, 1.5 + 0.2j), roughness=0.2,
-                 spec_coeff=0.4, diff_coeff=0.8)
-    grey = Glossy(diff_color=rgb(0.5, 0.5, 0.5), n=vec3(1.2 + 0.3j, 1.2 + 0.3j, 1.1 + 0.3j), roughness=0.2,
-                  spec_coeff=0.3, diff_coeff=0.9)
-    sc = Scene(ambient_color=rgb(0.05, 0.05, 0.05))
-    sc.add_Camera(look_from=vec3(0.3, 0.6, 1.8), look_at=vec3(0.0, 0.0, -1.0), screen_width=64, screen_height=48)
-    sc.add_DirectionalLight(Ldir=vec3(0.52, 0.45, -0.5), color=rgb(0.5, 0.5, 0.5))
-    sc.add(TriangleMesh(path, center=vec3(0.35, 0.05, -1.0), material=red, max_ray_depth=3))
-    sc.add(Plane(material=grey, center=vec3(0, -0.5, -2.0), width=40.0, height=40.0, u_axis=vec3(1.0, 0, 0),
-                 v_axis=vec3(0, 0, -1.0), max_ray_depth=3))
-    return sc
-
-
 def test_gpu_another_scene_with_the_same_tables_after_a_deformed_one(objs):
     """A deformed mesh's table holds the loaded shape, so a fresh Scene of the same OBJ has the resident signature
     while the device holds the deformed records and boxes: it must be uploaded all the same.  Nothing is rendered
@@ -229,15 +211,15 @@ def test_gpu_another_scene_with_the_same_tables_after_a_deformed_one(objs):
     from sightpy._lower import lower_scene
 
     B = _backend()
-    sc = _plain_scene(objs["ico2"])
+    sc = scenes.plain_mesh_scene(objs["ico2"])
     mesh = MD.mesh_of(sc)
     mesh.set_vertices(MD.twist(mesh.file_vertices))
     jit = _jitter(sc)
-    B._STATE["scene_sig"].clear()
+    B.forget_resident()
     deformed = _render(sc, jit)
     assert np.isin(deformed.hit_ids, _mesh_ids(sc)).sum() >= 50
     for posed in (False, True):
-        fresh = _plain_scene(objs["ico2"])
+        fresh = scenes.plain_mesh_scene(objs["ico2"])
         if posed:  # device-posed, in the rest pose and the loaded shape: an entry of Lowered.posed without vertices
             MD.mesh_of(fresh).set_pose(np.eye(3))
         assert lower_scene(fresh).signature() == lower_scene(sc).signature()  # (what makes the case)
@@ -412,7 +394,7 @@ def test_gpu_deform_entry_points_refusals(objs):
         finally:
             lib.srt_destroy(other)
     finally:
-        B._STATE["scene_sig"].clear()
+        B.forget_resident()
 
 
 def test_gpu_a_deformed_mesh_is_refused_on_several_gpus(objs, monkeypatch):

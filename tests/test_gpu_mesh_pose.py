@@ -131,7 +131,7 @@ def test_gpu_linear_loop_against_the_refitted_bvh(objs):
         off = _render(sc, jit)
     finally:
         _set_option("bvh", 1)
-        B._STATE["scene_sig"].clear()
+        B.forget_resident()
     assert np.array_equal(on.hit_ids, off.hit_ids)
     assert np.array_equal(on.rgb, off.rgb) and np.array_equal(on.srgb8, off.srgb8)
     assert np.isin(on.hit_ids, _mesh_ids(sc)).mean() > 0.02
@@ -144,7 +144,7 @@ def test_gpu_no_drift_over_a_pose_sequence(objs):
     sc = scenes.mesh_scene(objs["ico2"])
     mesh = _meshes(sc)[0]
     jit = _jitter(sc)
-    B._STATE["scene_sig"].clear()
+    B.forget_resident()
     frames, cost = [], []
     for pose in (None, (SKEW, SHIFT), POSE_B, (np.eye(3), (0.0, 0.0, 0.0))):
         if pose is not None:
@@ -166,8 +166,7 @@ def test_gpu_no_drift_over_a_pose_sequence(objs):
         made = B._STATE["ctx"]
         B._STATE["ctx"] = old
         if made is not None and made is not old:
-            B._STATE["scene_sig"].pop(made.value, None)
-            B._STATE["pose_sig"].pop(made.value, None)
+            B.forget_resident(made)
             lib.srt_destroy(made)
     assert new is not old
     assert np.array_equal(fresh.hit_ids, frames[0].hit_ids) and np.array_equal(fresh.rgb, frames[0].rgb)
@@ -214,7 +213,7 @@ def test_gpu_ranges_on_either_side_of_a_wave(objs):
         N.check(lib, lib.srt_pose_colliders(ctx, 4, N.ptr(first), N.ptr(count), N.ptr(poses)))
         got = _render(sc, jit)  # (the same tables are resident: nothing is uploaded or posed again)
     finally:
-        B._STATE["scene_sig"].clear()
+        B.forget_resident()
     V, Nn, UV = MP.mesh_arrays(mesh)
     for f, n, pose in ranges:
         V[f - 1:f - 1 + n] = MP.posed_vertices(V[f - 1:f - 1 + n], pose)
@@ -275,7 +274,7 @@ def test_gpu_pose_colliders_refusals(objs):
         finally:
             lib.srt_destroy(other)
     finally:
-        B._STATE["scene_sig"].clear()
+        B.forget_resident()
 
 
 def test_gpu_guides_of_a_posed_scene(objs):

@@ -166,7 +166,7 @@ def main():
         out["smooth_twist_30_deg_kernels"] = deform_times(lib, ctx)[0]
         mesh.invalidate()  # (the deformation is dropped: the static scene is uploaded again)
     # the static frame once more, later in the process: how far one process's figures move on their own
-    B._STATE["scene_sig"].clear()
+    B.forget_resident()
     out["static_again"] = runs(sc, a, first=False)
     lib, ctx = B.context()
     N.check(lib, lib.srt_set_option(ctx, b"pipeline", 0))  # (frames_ms turned it on)
